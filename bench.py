@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GCUPS of the SSV hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR]
 
 With --gpus N > 1 and no launcher around it (WORLD_SIZE unset) this script starts its own N workers
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py ...`, as a child process, before
@@ -356,6 +356,32 @@ class OrderedHits:
         return part[keep].cpu().numpy().view(np.uint64)
 
 
+DUMP_MAX_RECORDS = 2_000_000        # 24 B per record dumped (row, column, index as float64): at most 48 MB
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, merged) -> None:
+    """Write the ordered record list of the last timed pass -- what a caller of the path receives -- as float64 .npy files:
+    hit_rows (pHMM row), hit_columns (database column) and hit_index (the record's place in the list), plus num_hits.
+    Above DUMP_MAX_RECORDS records a fixed, seeded sample of places is written (hit_index says which, ascending)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(merged.numel())
+    if n <= DUMP_MAX_RECORDS:
+        index = np.arange(n, dtype=np.int64)
+        part = merged.cpu().numpy().view(np.uint64)
+    else:
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_MAX_RECORDS, replace=False)).astype(np.int64)
+        part = merged[torch.from_numpy(index).to(merged.device)].cpu().numpy().view(np.uint64)
+    rows = part >> np.uint64(40)
+    cols = ((part >> np.uint64(14)) & np.uint64(0x3FFFFFF)) * np.uint64(SEGMENT) + (part & np.uint64(0x3FFF))
+    # every value is below 2^53: float64 holds it exactly
+    np.save(os.path.join(out_dir, "hit_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "hit_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(out_dir, "hit_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(out_dir, "num_hits.npy"), np.array([n], dtype=np.float64))
+
+
 def gathered_list_checks(merged, counts, spans):
     """Order, duplicates, counts and columns-per-rank of a gathered list, on the device and through the C ABI
     (havac_ssv_check_order: one grid-stride HIP pass, no list-sized temporary, 64-bit indices).  Not torch: C4's list is
@@ -485,12 +511,17 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
     ap.add_argument("--pmc-timeout", type=int, default=240)
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed region, write the last timed pass's ordered hit list (rows, columns) to DIR/*.npy as "
+                         "float64 (a fixed, seeded sample above 2M records); the inputs are the same on every run")
     args = ap.parse_args()
     w = WORKLOADS[args.workload]
     if args.steps is None:
         args.steps = w["steps"]
     if args.warmup is None:
         args.warmup = w["warmup"]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.pmc_child:
         return pmc_child(args)
 
@@ -753,6 +784,8 @@ def main():
                 "gather_ms_rank0": round(float(np.mean(gather_ms)), 4) if gather_ms else None,
                 "per_rank": per_rank,
             }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, merged)
         cores = min(16, len(os.sched_getaffinity(0)))   # a 1-GPU box's CPU share
         ordered = OrderedHits(merged, nrows)
         watchdog.stage("checks of the list on rank 0 (CPU checker)", limit_s=max(args.deadline, 900.0))

@@ -4,7 +4,7 @@
 // A maintainer of the reference replaces host/HavacHwClient.{hpp,cpp} by this one file and links libhavac_dev.so
 // instead of xrt_coreutil / uuid / xilinxopencl (CMakeLists.txt:61-66).  host/Havac.cpp, host/phmm/PhmmPreprocessor.cpp,
 // host/sequence/SequencePreprocessor.cpp and PhmmReprojection/PhmmReprojection.cpp compile against it UNCHANGED:
-// tests/refhost/Makefile does exactly that, from where those files lie, and tests/test_gpu_refhost.py runs the result
+// oracle/refhost.mk does exactly that, from where those files lie, and tests/test_gpu_refhost.py runs the result
 // on the GPU next to this repository's own Havac.
 //
 // Class name, method names, argument types, return types and exception types are the reference's.  `ert_cmd_state`

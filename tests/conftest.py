@@ -20,9 +20,10 @@ def pytest_configure(config):
 
 def golden_names():
     """the SSV fixtures (packed sequence, model, hits); g7_* holds the projection's known answers (test_projection_golden.py),
-    g8_* the reference's per-(model, record) SSV on small files (test_boundary_golden.py)"""
+    g8_* the reference's per-(model, record) SSV on small files (test_boundary_golden.py), g9_* the reference's softSsv on
+    random sweeps (test_oracle.py)"""
     names = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
-    return [n for n in names if not n.startswith(("g7_", "g8_"))]
+    return [n for n in names if not n.startswith(("g7_", "g8_", "g9_"))]
 
 
 def load_golden(name):

@@ -6,7 +6,7 @@ Run in the build container only (needs /root/reference):
 
 The answers come from HitsFromSsv (host/test/Ssv.cpp:8-68) -- the function the reference's on-FPGA test compares the
 device with (host/test/RefernceComparisonTest/ReferenceComparisonTest.cpp:52-128) and the one boundary mode (SURVEY.md
-section 8 row f2) claims to match -- compiled from where it lies by tests/refhost/Makefile against the product's reader
+section 8 row f2) claims to match -- compiled from where it lies by oracle/refhost.mk against the product's reader
 headers (the reference's reader libraries are un-vendored: a differential build, like G7's).
 
 Each fixture is data only: the FASTA text, the HMMER3/f text, the p-value, and HitsFromSsv's hits as rows

@@ -1,5 +1,5 @@
-"""ctypes view of tests/_refhost/libhavac_refhost.so: the REFERENCE's own `Havac` class (host/Havac.cpp, compiled from
-where it lies by tests/refhost/Makefile in the build container) running over this repository's C ABI through
+"""ctypes view of oracle/_ref/libhavac_refhost.so: the REFERENCE's own `Havac` class (host/Havac.cpp, compiled from
+where it lies by oracle/refhost.mk in the build container) running over this repository's C ABI through
 integration/HavacHwClient.hpp.  TEST INFRASTRUCTURE ONLY -- nothing under havac_amd/ or in bench.py imports this."""
 from __future__ import annotations
 
@@ -10,7 +10,8 @@ import subprocess
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.path.join(os.path.dirname(HERE), "_refhost")
+ORACLE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle")
+OUT = os.path.join(ORACLE, "_ref")
 REFHOST_LIB = os.path.join(OUT, "libhavac_refhost.so")
 SSV_REF2_LIB = os.path.join(OUT, "libssv_ref2.so")
 REFERENCE = "/root/reference"
@@ -36,9 +37,9 @@ SIGNATURES = {
 def build_if_possible() -> bool:
     """In the build container (the reference tree is there) run the committed recipe; on the GPU box use what travelled."""
     if os.path.isfile(os.path.join(REFERENCE, "host", "Havac.cpp")):
-        r = subprocess.run(["make", "-C", HERE], capture_output=True, text=True)
+        r = subprocess.run(["make", "-C", ORACLE, "-f", "refhost.mk"], capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError("tests/refhost/Makefile failed:\n" + r.stdout + r.stderr)
+            raise RuntimeError("oracle/refhost.mk failed:\n" + r.stdout + r.stderr)
     return os.path.isfile(REFHOST_LIB)
 
 

@@ -4,8 +4,8 @@
  * TEST INFRASTRUCTURE ONLY (like oracle/_ref): nothing under havac_amd/ and nothing in bench.py's timed region loads
  * the library this file is linked into.  This file is ours; the class it drives is the reference's host/Havac.cpp,
  * compiled -- with host/phmm/PhmmPreprocessor.cpp, host/sequence/SequencePreprocessor.cpp and
- * PhmmReprojection/PhmmReprojection.cpp -- from where those files lie under /root/reference by tests/refhost/Makefile
- * into tests/_refhost/libhavac_refhost.so.  No reference source is copied into this repository.
+ * PhmmReprojection/PhmmReprojection.cpp -- from where those files lie under /root/reference by oracle/refhost.mk
+ * into oracle/_ref/libhavac_refhost.so.  No reference source is copied into this repository.
  *
  * What the build substitutes, and nothing else:
  *   host/HavacHwClient.hpp   -> integration/HavacHwClient.hpp (the binding over include/havac_dev.h; the reference's

@@ -4,8 +4,8 @@
  * ReferenceComparisonTest.cpp:52-128) and the one boundary mode claims to match.
  *
  * TEST INFRASTRUCTURE ONLY.  This file is ours; HitsFromSsv, findThreshold256ScalingFactor and
- * emissionScoreToProjectedScore are the reference's, compiled from where they lie by tests/refhost/Makefile into
- * tests/_refhost/libssv_ref2.so, against the product's FastaVector.h / p7HmmReader.h (the reference's reader libraries
+ * emissionScoreToProjectedScore are the reference's, compiled from where they lie by oracle/refhost.mk into
+ * oracle/_ref/libssv_ref2.so, against the product's FastaVector.h / p7HmmReader.h (the reference's reader libraries
  * are un-vendored: a differential build, as for the projection).  Used in the build container only, by
  * tests/golden/make_golden_g8.py, to capture tests/golden/g8_boundary_*.npz.
  */

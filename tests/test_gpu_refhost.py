@@ -1,6 +1,6 @@
 """Drop-in, as a tested fact: the REFERENCE's own host code -- host/Havac.cpp:20-191, host/phmm/PhmmPreprocessor.cpp:9-31,
 host/sequence/SequencePreprocessor.cpp:9-84, PhmmReprojection/PhmmReprojection.cpp -- compiled unchanged from where it
-lies (tests/refhost/Makefile, build container) against integration/HavacHwClient.hpp, runs on the GPU over the C ABI of
+lies (oracle/refhost.mk, build container) against integration/HavacHwClient.hpp, runs on the GPU over the C ABI of
 include/havac_dev.h, next to this repository's own `Havac`, on the same files with the same srand().
 
 Differential, not absolute: the FASTA / HMMER3 reader libraries the reference links are un-vendored, so both sides read
@@ -21,7 +21,7 @@ from test_gpu_api import write_inputs
 pytestmark = pytest.mark.gpu
 
 if not os.path.isfile(binding.REFHOST_LIB):
-    pytest.skip("tests/_refhost/libhavac_refhost.so was not built (it is made in the build container, where the "
+    pytest.skip("oracle/_ref/libhavac_refhost.so was not built (it is made in the build container, where the "
                 "reference tree is, and travels to the GPU box)", allow_module_level=True)
 
 libc = C.CDLL(None)
