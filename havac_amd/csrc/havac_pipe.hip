@@ -266,27 +266,40 @@ extern "C" int havac_pipe_collect(havac_pipe* p, uint64_t* found_out, const uint
 // `nsteps` passes of the same inputs, as many in flight as the pipe is deep, all complete on return: the loop a caller makes --
 // submit, and collect the oldest once every slot is in flight -- without the caller's language in it (bench.py's timed regions:
 // what is measured is then what a C++ caller of this library gets).  kernel_ms / total_ms (nsteps entries each, may be NULL)
-// receive every pass's havac_pipe_last_ms; the last pass's result as havac_pipe_collect returns it.
+// receive every pass's havac_pipe_last_ms; the last pass's result as havac_pipe_collect returns it.  The pipe must be idle on
+// entry, and it is idle on return whatever happened: after the first failed submit or collect the passes still in flight are
+// collected (their results dropped) and that first error is returned.
 extern "C" int havac_pipe_run(havac_pipe* p, uint32_t nsteps, const uint8_t* d_sequence, uint64_t nsymbols, const int8_t* d_phmm, uint32_t nrows,
                               uint32_t shard_index, uint32_t shard_count, void* caller_stream, float* kernel_ms, float* total_ms,
                               uint64_t* found_out, const uint64_t** d_records_out, uint64_t* nrecords_out) {
     if (!p) return HAVAC_E_ARGUMENT;
+    if (!p->in_flight.empty()) { p->err = "passes are in flight: collect them before havac_pipe_run"; return HAVAC_E_LOGIC; }
     uint32_t collected = 0;
     auto collect = [&]() -> int {
         const int rc = havac_pipe_collect(p, found_out, d_records_out, nrecords_out, caller_stream);
         if (rc) return rc;
         float k = 0.f, t = 0.f;
         (void)havac_pipe_last_ms(p, &k, &t);
-        if (kernel_ms) kernel_ms[collected] = k;
-        if (total_ms) total_ms[collected] = t;
+        if (collected < nsteps) {
+            if (kernel_ms) kernel_ms[collected] = k;
+            if (total_ms) total_ms[collected] = t;
+        }
         collected++;
         return HAVAC_OK;
     };
+    auto drain = [&](int rc) -> int {
+        const std::string err = p->err;
+        // (bounded: a collect that fails before it takes its pass off in_flight must not keep the loop going)
+        for (size_t left = p->in_flight.size(); left > 0 && !p->in_flight.empty(); left--)
+            (void)havac_pipe_collect(p, nullptr, nullptr, nullptr, caller_stream);
+        p->err = err;
+        return rc;
+    };
     for (uint32_t i = 0; i < nsteps; i++) {
-        if (int rc = havac_pipe_submit(p, d_sequence, nsymbols, d_phmm, nrows, shard_index, shard_count, nullptr, i == 0 ? caller_stream : HAVAC_NO_STREAM)) return rc;
-        if (p->in_flight.size() == p->depth) { if (int rc = collect()) return rc; }
+        if (int rc = havac_pipe_submit(p, d_sequence, nsymbols, d_phmm, nrows, shard_index, shard_count, nullptr, i == 0 ? caller_stream : HAVAC_NO_STREAM)) return drain(rc);
+        if (p->in_flight.size() == p->depth) { if (int rc = collect()) return drain(rc); }
     }
-    while (!p->in_flight.empty()) { if (int rc = collect()) return rc; }
+    while (!p->in_flight.empty()) { if (int rc = collect()) return drain(rc); }
     return HAVAC_OK;
 }
 

@@ -162,22 +162,38 @@ void Havac::runHardwareClientAsync() {
     if (!sequenceLoadedToDevice)   // :89-91
         throw std::logic_error("Sequence was not loaded to device before hardware was requested to run.");
     needDevice();
+    RunInputs inputs = currentInputs();
     check(havac_dev_run_async(dev_));
-    // the models this run's hits belong to (host/Havac.cpp:104-116 makes the prefix sums when the hits are fetched; here the
-    // model list may have been replaced by then)
-    RunModels m;
-    m.prefixSums = generatePhmmLenPrefixSums();
-    for (uint32_t i = 0; i < p7HmmList->count; i++) m.lengths.push_back(p7HmmList->phmms[i].header.modelLength);
-    m.starts = modelStarts_;
-    if (pipelineDepth_ == 1) runModels_.clear();           // (the finished run before this one was closed by the device layer too)
-    runModels_.push_back(std::move(m));
+    // the models and records this run's hits belong to (host/Havac.cpp:104-116 makes the prefix sums when the hits are fetched;
+    // here the model list may have been replaced by then, and the records extended).  The device layer may have closed finished
+    // runs to make room for this one -- at depth 1 the run before, deeper the oldest if it was finished and not fetched: their
+    // records go with them, so that the oldest record left is the oldest open run's.
+    const size_t older = havac_dev_open_runs(dev_) - 1;
+    while (runInputs_.size() > older) runInputs_.pop_front();
+    runInputs_.push_back(std::move(inputs));
+}
+
+Havac::RunInputs Havac::currentInputs() {
+    RunInputs r;
+    r.prefixSums = generatePhmmLenPrefixSums();
+    for (uint32_t i = 0; i < p7HmmList->count; i++) r.lengths.push_back(p7HmmList->phmms[i].header.modelLength);
+    r.starts = modelStarts_;
+    r.recordEnds.reserve(fastaVector->metadata.count);
+    for (size_t j = 0; j < fastaVector->metadata.count; j++) r.recordEnds.push_back(fastaVector->metadata.data[j].sequenceEndPosition);
+    r.recordStarts = recordStarts_;
+    r.recordLengths = recordLengths_;
+    r.residueCounts = residueCounts_;
+    r.bothStrands = bothStrands_;
+    r.forwardColumns = forwardColumns_;
+    return r;
 }
 
 void Havac::setPipelineDepth(uint32_t depth) {
     needDevice();
     check(havac_dev_set_pipeline_depth(dev_, depth));
     pipelineDepth_ = depth;
-    runModels_.clear();
+    // a new depth closes every run; the same depth leaves finished runs open, and their records with them
+    if (havac_dev_open_runs(dev_) == 0) runInputs_.clear();
 }
 
 void Havac::waitHardwareClientAsync() { needDevice(); check(havac_dev_wait(dev_, 0)); }
@@ -207,7 +223,11 @@ void Havac::setBothStrands(bool on) {
     bothStrands_ = on;
 }
 
-void Havac::setHitCapacity(uint64_t maxHits) { needDevice(); check(havac_dev_set_hit_capacity(dev_, maxHits)); }
+void Havac::setHitCapacity(uint64_t maxHits) {
+    needDevice();
+    check(havac_dev_set_hit_capacity(dev_, maxHits));
+    runInputs_.clear();                                    // (new hit buffers: the device layer has closed every run)
+}
 
 void Havac::lastRunMilliseconds(float *ssvKernelMs, float *totalMs) {
     needDevice();
@@ -222,7 +242,7 @@ vector<uint32_t> Havac::generatePhmmLenPrefixSums() {   // host/Havac.cpp:104-11
 }
 
 // largest index whose prefix sum is <= the global row (host/Havac.cpp:119-142)
-PhmmLocalPosition phmmPrefixSumsBinarySearch(uint32_t phmmGlobalPosition, vector<uint32_t> &prefixSums) {
+PhmmLocalPosition phmmPrefixSumsBinarySearch(uint32_t phmmGlobalPosition, const vector<uint32_t> &prefixSums) {
     int32_t lo = 0, hi = (int32_t)prefixSums.size() - 1, found = -1;
     while (lo <= hi) {
         int32_t mid = lo + (hi - lo) / 2;
@@ -235,21 +255,24 @@ PhmmLocalPosition phmmPrefixSumsBinarySearch(uint32_t phmmGlobalPosition, vector
 }
 
 // One raw record -> a HavacHit (host/Havac.cpp:150-184); false: a hit in the padding after the last record, dropped.
-static bool resolveOne(uint64_t rec, size_t index, const FastaVector *fastaVector, vector<uint32_t> &phmmPrefixSums, HavacHit *out) {
+// recordEnds: FastaVector's sequenceEndPosition of every record (fastaVectorGetLocalSequencePositionFromGlobal on them).
+static bool resolveOne(uint64_t rec, size_t index, const vector<uint64_t> &recordEnds, const vector<uint32_t> &phmmPrefixSums,
+                       HavacHit *out) {
     // [13:0] column in segment, [39:14] segment, [63:40] row (host/Havac.cpp:155-163)
     const uint64_t inSegment = rec & ((1ull << 14) - 1);
     const uint64_t segment = (rec & ((1ull << 40) - 1)) >> 14;
     const uint64_t globalSequencePosition = segment * (12 * 1024) + inSegment;
     const uint32_t globalPhmmPosition = (uint32_t)(rec >> 40);
-    FastaVectorLocalPosition local;
-    if (!fastaVectorGetLocalSequencePositionFromGlobal(fastaVector, globalSequencePosition, &local))
-        return false;   // a hit in the padding after the last record (host/Havac.cpp:169-173)
+    // the first record whose end lies beyond the column
+    const size_t record = std::upper_bound(recordEnds.begin(), recordEnds.end(), globalSequencePosition) - recordEnds.begin();
+    if (record == recordEnds.size()) return false;   // a hit in the padding after the last record (host/Havac.cpp:169-173)
+    const uint64_t positionInSequence = globalSequencePosition - (record ? recordEnds[record - 1] : 0);
     PhmmLocalPosition where = phmmPrefixSumsBinarySearch(globalPhmmPosition, phmmPrefixSums);
     if (where.phmmIndex == -1) {
         std::cerr << "ERROR: could not resolve phmm position for raw hit report #" << index << "\n" << std::endl;
         return false;
     }
-    *out = HavacHit(local.positionInSequence, (uint32_t)local.sequenceIndex, where.phmmPosition, (uint32_t)where.phmmIndex);
+    *out = HavacHit(positionInSequence, (uint32_t)record, where.phmmPosition, (uint32_t)where.phmmIndex);
     return true;
 }
 
@@ -278,23 +301,39 @@ static vector<HavacHit> resolveAll(size_t n, F &&fn) {
 }
 
 vector<HavacHit> havacResolveHits(const vector<uint64_t> &rawHits, const FastaVector *fastaVector,
-                                  vector<uint32_t> &phmmPrefixSums) {
-    return resolveAll(rawHits.size(), [&](size_t i, HavacHit *hit) { return resolveOne(rawHits[i], i, fastaVector, phmmPrefixSums, hit); });
+                                  const vector<uint32_t> &phmmPrefixSums) {
+    vector<uint64_t> ends(fastaVector->metadata.count);
+    for (size_t j = 0; j < ends.size(); j++) ends[j] = fastaVector->metadata.data[j].sequenceEndPosition;
+    return resolveAll(rawHits.size(), [&](size_t i, HavacHit *hit) { return resolveOne(rawHits[i], i, ends, phmmPrefixSums, hit); });
 }
 
 vector<HavacHit> Havac::getHitsFromFinishedRun() { return fetchHits(nullptr); }
 
-vector<HavacHit> Havac::fetchHits(vector<uint32_t> *modelLengthsOut) {
+vector<HavacHit> Havac::fetchHits(RunInputs *inputsOut) {
     needDevice();
+    // with several runs open, fetching a run's hits closes it -- also when it has no list (overflowed, aborted): the next call
+    // speaks of the next run, and the run's inputs go with it
+    struct CloseRun {
+        Havac *h;
+        ~CloseRun() { if (h->pipelineDepth_ > 1) { (void)havac_dev_retire(h->dev_); if (!h->runInputs_.empty()) h->runInputs_.pop_front(); } }
+    } closeRun{this};
+    rawHits_.clear();                                      // (a fetch that throws leaves no list of an earlier run behind)
+    // the models and records this run ran with (loadPhmm / loadSequence may have changed them since): one record per open run,
+    // kept in step with the device layer's runs (runHardwareClientAsync, setPipelineDepth, setHitCapacity, CloseRun)
+    const uint32_t open = havac_dev_open_runs(dev_);
+    if (open && runInputs_.size() != open)
+        throw std::logic_error("the runs recorded by Havac are out of step with the device layer's open runs");
     uint64_t n = 0;                                        // 64-bit: several GPUs can hold more than 2^32 - 1 records
-    check(havac_dev_num_hits64(dev_, &n));
+    check(havac_dev_num_hits64(dev_, &n));                 // (no open run: throws)
+    const RunInputs &run = runInputs_.front();             // (released before closeRun pops it)
+    if (inputsOut) *inputsOut = run;
     rawHits_.assign(n, 0);
     if (n) check(havac_dev_read_hits64(dev_, rawHits_.data(), n));
-    // both strands: a record of the second half is the record at (column - forwardColumns_) of the first.  Folded record by
+    // both strands: a record of the second half is the record at (column - forwardColumns) of the first.  Folded record by
     // record where it is resolved: no second copy of the list and no flag per record (with one strand -- the reference's
     // mode -- nothing at all is done: C4's list is 36 GB)
-    const bool bothStrands = bothStrands_;
-    const uint64_t forwardColumns = forwardColumns_;
+    const bool bothStrands = run.bothStrands;
+    const uint64_t forwardColumns = run.forwardColumns;
     auto fold = [bothStrands, forwardColumns](uint64_t rec, bool *isReverse) -> uint64_t {
         *isReverse = false;
         if (!bothStrands) return rec;
@@ -308,46 +347,32 @@ vector<HavacHit> Havac::fetchHits(vector<uint32_t> *modelLengthsOut) {
     auto mirror = [&](HavacHit &h, bool isReverse) {
         if (!isReverse) return;
         h.reverseStrand = true;
-        const uint64_t n = residueCounts_[h.sequenceIndex];
+        const uint64_t n = run.residueCounts[h.sequenceIndex];
         if (h.sequencePosition < n) h.sequencePosition = n - 1 - h.sequencePosition;   // the terminator column stays
     };
-    // the models this run ran with (a run started before loadPhmm replaced them; with nothing recorded: the current ones)
-    RunModels models;
-    if (!runModels_.empty()) models = runModels_.front();
-    else {
-        models.prefixSums = generatePhmmLenPrefixSums();
-        for (uint32_t i = 0; i < p7HmmList->count; i++) models.lengths.push_back(p7HmmList->phmms[i].header.modelLength);
-        models.starts = modelStarts_;
-    }
-    if (modelLengthsOut) *modelLengthsOut = models.lengths;
-    // with several runs open, fetching a run's hits closes it: the next call speaks of the next run
-    struct CloseRun {
-        Havac *h;
-        ~CloseRun() { if (h->pipelineDepth_ > 1) { (void)havac_dev_retire(h->dev_); if (!h->runModels_.empty()) h->runModels_.pop_front(); } }
-    } closeRun{this};
     if (!boundaryMode_) {
-        vector<uint32_t> &sums = models.prefixSums;
         return resolveAll(raw.size(), [&](size_t i, HavacHit *hit) {
             bool isReverse;
-            if (!resolveOne(fold(raw[i], &isReverse), i, fastaVector, sums, hit)) return false;
+            if (!resolveOne(fold(raw[i], &isReverse), i, run.recordEnds, run.prefixSums, hit)) return false;
             mirror(*hit, isReverse);
             return true;
         });
     }
     // boundary mode: records and models have their own start tables (separators in between)
-    const vector<uint32_t> &modelStarts_ = models.starts;
+    const vector<uint32_t> &modelStarts = run.starts;
+    const vector<uint64_t> &recordStarts = run.recordStarts, &recordLengths = run.recordLengths;
     return resolveAll(raw.size(), [&](size_t i, HavacHit *hit) {
         bool isReverse;
         const uint64_t rec = fold(raw[i], &isReverse);
         const uint64_t column = ((rec >> 14) & 0x3ffffffull) * 12288ull + (rec & 0x3fffull);
         const uint32_t row = (uint32_t)(rec >> 40);
-        size_t j = std::upper_bound(recordStarts_.begin(), recordStarts_.end(), column) - recordStarts_.begin();
-        size_t k = std::upper_bound(modelStarts_.begin(), modelStarts_.end(), row) - modelStarts_.begin();
+        size_t j = std::upper_bound(recordStarts.begin(), recordStarts.end(), column) - recordStarts.begin();
+        size_t k = std::upper_bound(modelStarts.begin(), modelStarts.end(), row) - modelStarts.begin();
         if (j == 0 || k == 0) return false;
         j--; k--;
-        if (column - recordStarts_[j] >= recordLengths_[j]) return false;                     // separator or padding column
-        if (row - modelStarts_[k] >= models.lengths[k]) return false;                         // separator row
-        *hit = HavacHit(column - recordStarts_[j], (uint32_t)j, row - modelStarts_[k], (uint32_t)k);
+        if (column - recordStarts[j] >= recordLengths[j]) return false;                       // separator or padding column
+        if (row - modelStarts[k] >= run.lengths[k]) return false;                             // separator row
+        *hit = HavacHit(column - recordStarts[j], (uint32_t)j, row - modelStarts[k], (uint32_t)k);
         mirror(*hit, isReverse);
         return true;
     });
@@ -402,16 +427,15 @@ vector<HavacWindow> havacMergeHitsToWindows(const vector<HavacHit> &hits, const 
 }
 
 vector<HavacWindow> Havac::getWindowsFromFinishedRun(uint32_t flank) {
-    vector<uint32_t> modelLengths;
-    vector<HavacHit> hits = fetchHits(&modelLengths);
+    RunInputs run;
+    vector<HavacHit> hits = fetchHits(&run);
     vector<uint64_t> recordLengths;
-    size_t start = 0;
-    for (size_t i = 0; i < fastaVector->metadata.count; i++) {          // end position is one past the terminator
-        const size_t end = fastaVector->metadata.data[i].sequenceEndPosition;
+    uint64_t start = 0;
+    for (const uint64_t end : run.recordEnds) {                        // end position is one past the terminator
         recordLengths.push_back(end > start ? end - start - 1 : 0);
         start = end;
     }
-    return havacMergeHitsToWindows(hits, modelLengths, recordLengths, flank);
+    return havacMergeHitsToWindows(hits, run.lengths, recordLengths, flank);
 }
 
 HavacHit::HavacHit(const uint64_t sequencePosition, const uint32_t sequenceIndex, const uint32_t phmmPosition,

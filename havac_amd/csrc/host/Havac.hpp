@@ -145,19 +145,28 @@ private:
     vector<uint64_t> residueCounts_;                       // both strands: residues per record
     vector<uint64_t> recordStarts_, recordLengths_;        // boundary mode: global column of each record
     vector<uint32_t> modelStarts_;                         // boundary mode: global row of each model
-    // what a run's hits are resolved against: the models it was started with (loadPhmm may have replaced them since)
-    struct RunModels { vector<uint32_t> prefixSums, lengths, starts; };
-    std::deque<RunModels> runModels_;                      // one per open run, oldest first
+    // what a run's hits are resolved against: the models and records it was started with (loadPhmm may have replaced the
+    // models since, loadSequence may have added records or a second strand)
+    struct RunInputs {
+        vector<uint32_t> prefixSums, lengths, starts;      // models: prefix sums of the lengths, lengths, boundary-mode rows
+        vector<uint64_t> recordEnds;                       // FastaVector sequenceEndPosition of every record
+        vector<uint64_t> recordStarts, recordLengths;      // boundary mode
+        vector<uint64_t> residueCounts;                    // both strands
+        bool bothStrands = false;
+        uint64_t forwardColumns = 0;
+    };
+    RunInputs currentInputs();
+    std::deque<RunInputs> runInputs_;                      // one per open run, oldest first
     uint32_t pipelineDepth_ = 1;
-    vector<HavacHit> fetchHits(vector<uint32_t> *modelLengthsOut);
+    vector<HavacHit> fetchHits(RunInputs *inputsOut);
 };
 
 // The resolver of host/Havac.cpp:145-187 as a free function (testable without a device):
 // raw 64-bit records -> HavacHit, dropping hits in the padding after the last record.
 struct PhmmLocalPosition { int32_t phmmIndex; uint32_t phmmPosition; };
-PhmmLocalPosition phmmPrefixSumsBinarySearch(uint32_t phmmGlobalPosition, vector<uint32_t> &prefixSums);
+PhmmLocalPosition phmmPrefixSumsBinarySearch(uint32_t phmmGlobalPosition, const vector<uint32_t> &prefixSums);
 vector<HavacHit> havacResolveHits(const vector<uint64_t> &rawHits, const FastaVector *fastaVector,
-                                  vector<uint32_t> &phmmPrefixSums);
+                                  const vector<uint32_t> &phmmPrefixSums);
 
 // Hits -> merged windows, as a free function (testable without a device).  A hit at model position k (0-based, model
 // length L) and record position i covers [i - k, i + (L-1-k)] on the forward strand and [i - (L-1-k), i + k] on the

@@ -18,6 +18,9 @@ struct havac_host {
     std::string err;
     vector<HavacHit> hits;
     bool haveHits = false;
+    vector<HavacWindow> windows;                 // the same for havac_host_get_windows (with the flank they were made with)
+    bool haveWindows = false;
+    uint32_t windowsFlank = 0;
     uint32_t depth = 1;
 };
 
@@ -93,22 +96,29 @@ const char *havac_host_last_error(havac_host *h) { return h ? h->err.c_str() : "
 
 int havac_host_load_sequence(havac_host *h, const char *p) { return guarded(h, [&] { h->obj->loadSequence(p); }); }
 int havac_host_load_phmm(havac_host *h, const char *p) { return guarded(h, [&] { h->obj->loadPhmm(p); }); }
-int havac_host_run(havac_host *h) { h->haveHits = false; return guarded(h, [&] { h->obj->runHardwareClient(); }); }
-int havac_host_run_async(havac_host *h) { h->haveHits = false; return guarded(h, [&] { h->obj->runHardwareClientAsync(); }); }
+int havac_host_run(havac_host *h) { h->haveHits = h->haveWindows = false; return guarded(h, [&] { h->obj->runHardwareClient(); }); }
+int havac_host_run_async(havac_host *h) {
+    h->haveHits = h->haveWindows = false;
+    return guarded(h, [&] { h->obj->runHardwareClientAsync(); });
+}
 int havac_host_wait(havac_host *h) { return guarded(h, [&] { h->obj->waitHardwareClientAsync(); }); }
 int havac_host_abort(havac_host *h) { return guarded(h, [&] { h->obj->abortHardwareClient(); }); }
-int havac_host_set_hit_capacity(havac_host *h, uint64_t n) { return guarded(h, [&] { h->obj->setHitCapacity(n); }); }
-int havac_host_set_pipeline_depth(havac_host *h, uint32_t depth) {
-    const int rc = guarded(h, [&] { h->obj->setPipelineDepth(depth); });
-    if (rc == HAVAC_OK) { h->depth = depth; h->haveHits = false; }
+int havac_host_set_hit_capacity(havac_host *h, uint64_t n) {
+    const int rc = guarded(h, [&] { h->obj->setHitCapacity(n); });
+    if (rc == HAVAC_OK) h->haveHits = h->haveWindows = false;     // (new hit buffers: every run is closed)
     return rc;
 }
-// With several runs open havac_host_get_hits fetches (and closes) the oldest run once and then serves the copy it keeps -- a
-// caller asks twice, for the count and for the arrays; this says the caller is done with that run: the next havac_host_get_hits
-// fetches the next one.  At depth 1 the copy is kept until the next run, as the reference's getHitsFromFinishedRun can be
+int havac_host_set_pipeline_depth(havac_host *h, uint32_t depth) {
+    const int rc = guarded(h, [&] { h->obj->setPipelineDepth(depth); });
+    if (rc == HAVAC_OK) { h->depth = depth; h->haveHits = h->haveWindows = false; }
+    return rc;
+}
+// With several runs open havac_host_get_hits (havac_host_get_windows) fetches (and closes) the oldest run once and then serves the
+// copy it keeps -- a caller asks twice, for the count and for the arrays; this says the caller is done with that run: the next
+// havac_host_get_hits (havac_host_get_windows) fetches the next one.  At depth 1 the copy is kept until the next run, as the reference's getHitsFromFinishedRun can be
 // called again and again.
 int havac_host_next_run(havac_host *h) {
-    if (h->depth > 1) h->haveHits = false;
+    if (h->depth > 1) h->haveHits = h->haveWindows = false;
     return HAVAC_OK;
 }
 int havac_host_set_both_strands(havac_host *h, int on) { return guarded(h, [&] { h->obj->setBothStrands(on != 0); }); }
@@ -129,6 +139,9 @@ int havac_host_state(havac_host *h) {
 int havac_host_get_hits(havac_host *h, uint64_t *sp, uint32_t *si, uint32_t *pp, uint32_t *pi, uint32_t cap,
                         uint32_t *count) {
     if (!h->haveHits) {
+        // a fetch that throws has closed its run at depth > 1 (Havac::fetchHits): haveHits stays false, so the next call fetches
+        // the next run, and no list of an earlier run is served in the meantime
+        h->hits.clear();
         int rc = guarded(h, [&] { h->hits = h->obj->getHitsFromFinishedRun(); });
         if (rc != HAVAC_OK) return rc;
         h->haveHits = true;
@@ -149,10 +162,15 @@ static int copyWindows(const vector<HavacWindow> &w, uint32_t *si, uint32_t *pi,
 
 int havac_host_get_windows(havac_host *h, uint32_t flank, uint32_t *si, uint32_t *pi, uint8_t *rs, uint64_t *start,
                            uint64_t *end, uint32_t *pf, uint32_t *pl, uint32_t *hc, uint32_t cap, uint32_t *count) {
-    vector<HavacWindow> w;
-    int rc = guarded(h, [&] { w = h->obj->getWindowsFromFinishedRun(flank); });
-    if (rc != HAVAC_OK) return rc;
-    return copyWindows(w, si, pi, rs, start, end, pf, pl, hc, cap, count);
+    if (!h->haveWindows || h->windowsFlank != flank) {
+        h->windows.clear();
+        h->haveWindows = false;
+        int rc = guarded(h, [&] { h->windows = h->obj->getWindowsFromFinishedRun(flank); });
+        if (rc != HAVAC_OK) return rc;
+        h->haveWindows = true;
+        h->windowsFlank = flank;
+    }
+    return copyWindows(h->windows, si, pi, rs, start, end, pf, pl, hc, cap, count);
 }
 
 int havac_host_merge_windows(const uint64_t *sp, const uint32_t *sidx, const uint32_t *pp, const uint32_t *pidx,

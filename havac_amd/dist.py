@@ -467,8 +467,7 @@ class ShardedSsv:
         rc = self._L.havac_pipe_run(self._h, nsteps, d_seq.data_ptr(), nsymbols, d_phmm.data_ptr(), nrows, self.rank, self.world,
                                     _NO_STREAM if inputs_ready and not self._gathers else (current.cuda_stream or None), k_ms, t_ms,
                                     C.byref(found), C.byref(ptr), C.byref(n))
-        self._next = (self._next + nsteps) % self.depth
-        self.ctx = self._contexts[(self._next - 1) % self.depth]
+        self._sync_with_pipe()      # (a failed run stops early: how far it got is the pipe's to say)
         if rc < 0:
             try:
                 self._check(rc)
@@ -480,6 +479,14 @@ class ShardedSsv:
         if not self._gathers:
             return (_records_tensor(ptr.value, found.value, self.device, self._capacity), found.value), timings
         return ((_records_tensor(ptr.value, n.value, self.device) if self.rank == 0 else None), found.value), timings
+
+    def _sync_with_pipe(self):
+        """the mirror (next slot, passes in flight, context of the last collected pass) read back from the pipe itself"""
+        handles = [ctx.handle for ctx in self._contexts]
+        self._next = handles.index(self._L.havac_pipe_context(self._h, -2))
+        self.ctx = self._contexts[handles.index(self._L.havac_pipe_context(self._h, -1))]
+        n = int(self._L.havac_pipe_in_flight(self._h))
+        self.in_flight = [(self._next - n + i) % self.depth for i in range(n)]
 
     def wait_gathers(self):
         """The records of the last collected pass may still be travelling (the gather is enqueued, not waited for): waits for
@@ -513,6 +520,8 @@ class ShardedSsv:
         if self.in_flight:
             raise RuntimeError("passes are in flight: collect() them first")
         self._check(self._L.havac_pipe_release(self._h))
+        for ctx in self._contexts:      # (the slots' contexts are freed: the borrowed handles must not reach the library again)
+            ctx.close()
         self._merged = [None] * self.depth
         _views.clear()
         torch.cuda.empty_cache()

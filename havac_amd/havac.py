@@ -187,6 +187,7 @@ class Havac:
         self._check(self._L.havac_host_get_windows(self._h, flank, *([None] * 8), 0, C.byref(n)))
         arrays = _window_arrays(n.value)
         self._check(self._L.havac_host_get_windows(self._h, flank, *[a.ctypes.data for a in arrays], n.value, C.byref(n)))
+        self._L.havac_host_next_run(self._h)      # (several runs open: the next call fetches the next run)
         return _windows_from_arrays(arrays, n.value)
 
     def rawHits(self) -> np.ndarray:

@@ -23,17 +23,36 @@ class SsvContext:
 
     @classmethod
     def borrowed(cls, handle):
-        """a context that somebody else owns (a slot of a pipe: havac_pipe_context); close() leaves it alone"""
+        """a context that somebody else owns (a slot of a pipe: havac_pipe_context); close() leaves it alone, and the owner
+        closes this view when it frees the context"""
         self = cls.__new__(cls)
         self._L = _lib.load()
         self._h = C.c_void_p(handle)
         self._borrowed = True
         return self
 
+    @property
+    def _h(self):
+        h = self.__dict__.get("_handle")
+        if h is None:
+            raise RuntimeError("the SSV context is closed (or its owner has released it)")
+        return h
+
+    @_h.setter
+    def _h(self, h):
+        self.__dict__["_handle"] = h
+
+    @property
+    def handle(self):
+        """the address of the C context (None once closed)"""
+        h = self.__dict__.get("_handle")
+        return h.value if h is not None else None
+
     def close(self):
-        if getattr(self, "_h", None):
+        h = self.__dict__.get("_handle")
+        if h:
             if not getattr(self, "_borrowed", False):
-                self._L.havac_ssv_ctx_destroy(self._h)
+                self._L.havac_ssv_ctx_destroy(h)
             self._h = None
 
     __del__ = close

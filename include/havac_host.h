@@ -111,7 +111,9 @@ int havac_host_merge_windows(const uint64_t *sequence_position, const uint32_t *
                              uint32_t *w_sequence_index, uint32_t *w_phmm_index, uint8_t *w_reverse_strand,
                              uint64_t *w_start, uint64_t *w_end, uint32_t *w_phmm_first, uint32_t *w_phmm_last,
                              uint32_t *w_hit_count, uint32_t cap, uint32_t *count);
-/* The same on a handle's finished run (Havac::getWindowsFromFinishedRun). */
+/* The same on a handle's finished run (Havac::getWindowsFromFinishedRun).  Fetched once and then served from a copy, as
+ * havac_host_get_hits is (ask for the count, then the arrays, with the same flank); with several runs open,
+ * havac_host_next_run says the caller is done with that run. */
 int havac_host_get_windows(havac_host *h, uint32_t flank, uint32_t *w_sequence_index, uint32_t *w_phmm_index,
                            uint8_t *w_reverse_strand, uint64_t *w_start, uint64_t *w_end, uint32_t *w_phmm_first,
                            uint32_t *w_phmm_last, uint32_t *w_hit_count, uint32_t cap, uint32_t *count);
