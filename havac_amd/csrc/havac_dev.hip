@@ -26,23 +26,11 @@
 
 #include "ssv_kernels.hip.h"
 #include "hit_order.hip.h"
+#include "hip_memory.h"
 
 using namespace havac;
 
 namespace {
-
-std::string hip_msg(const char* what, hipError_t e) {
-    return std::string(what) + ": " + hipGetErrorString(e);
-}
-
-#define HIP_TRY(ctx_err, expr)                                        \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            (ctx_err) = hip_msg(#expr, _e);                           \
-            return _e == hipErrorOutOfMemory ? HAVAC_E_NOMEM : HAVAC_E_RUNTIME; \
-        }                                                             \
-    } while (0)
 
 inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 
@@ -317,24 +305,26 @@ inline size_t handoff_slots(const SsvRare& L) {
 // ===========================================================================
 struct havac_ssv_ctx {
     int device = 0;
-    uint32_t* rows8 = nullptr; size_t rows8_rows = 0;   // padded copy of the model
-    uint32_t* chunk_flags = nullptr; size_t chunk_flag_words = 0;   // one byte per 32-row chunk, bit Q: window Q may test for hits at its end only
+    DeviceBuffer<uint32_t> rows8;                       // padded copy of the model
+    DeviceBuffer<uint32_t> chunk_flags;                 // one byte per 32-row chunk, bit Q: window Q may test for hits at its end only
     // work distribution of the persistent kernel (ssv_kernels.hip.h, SsvLaunch)
     // the words a pass's kernels count in, cleared by ssv_prepare_model in front of every pass: [0, 144) the ticket counters of cut
     // tiles and the fault word, [144, 160) the ordering's OrderState (hit_order.hip.h)
-    uint32_t* control = nullptr;
-    uint32_t* block_flags = nullptr; size_t block_flag_tiles = 0;   // row-split launches: row blocks finished, per tile
-    uint32_t* block_state = nullptr; size_t block_state_tiles = 0;  // row-split launches: 16 x 64 scores per tile
-    uint64_t* tails = nullptr; uint32_t* tail_counts = nullptr; size_t tail_blocks = 0;   // block tails (ssv_kernels.hip.h): kTailSlots keys + a count per block
+    DeviceBuffer<uint32_t> control;
+    // row-split launches, per hand-off slot: the row blocks finished, 16 x 64 scores (the capacity of block_flags counts the slots of both)
+    DeviceBuffer<uint32_t> block_flags, block_state;
+    // block tails (ssv_kernels.hip.h): kTailSlots keys + a count per block (the capacity of tail_counts counts the blocks of both)
+    DeviceBuffer<uint64_t> tails; DeviceBuffer<uint32_t> tail_counts;
     int resident_blocks = 0;                                        // blocks the device holds at once (6 per CU)
     const uint16_t* pair_mask = nullptr;                // optional separator bitmap (boundary mode), caller-owned
-    void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
-    uint64_t* sort_alt = nullptr; size_t sort_alt_count = 0;
-    // the ordering (hit_order.hip.h, ssv_order_pass): per bucket a count / cursor and an offset, the list of large buckets
-    uint32_t* bucket_counts = nullptr; uint32_t* bucket_offsets = nullptr; uint64_t* bucket_chunk_base = nullptr;
-    uint32_t* bucket_large = nullptr; size_t bucket_alloc = 0;
+    DeviceBuffer<uint8_t> sort_tmp;
+    DeviceBuffer<uint64_t> sort_alt;
+    // the ordering (hit_order.hip.h, ssv_order_pass): per bucket a count / cursor and an offset, the list of large buckets (the
+    // capacity of bucket_counts counts the buckets of all four)
+    DeviceBuffer<uint32_t> bucket_counts, bucket_offsets; DeviceBuffer<uint64_t> bucket_chunk_base;
+    DeviceBuffer<uint32_t> bucket_large;
     uint32_t large_capacity = kLargeBucketDefault;   // keys the ordering kernel's LDS sorter holds in the next launch (grown on demand)
-    PassReport* h_report = nullptr;            // pinned: what the pass's ordering kernel tells the host
+    PinnedBuffer<PassReport> h_report;         // what the pass's ordering kernel tells the host
     OrderPass order_args{};                    // of the pending pass (a relaunch after growing a buffer reuses them)
     uint32_t order_tail_blocks = 0;            // blocks whose tails the pending pass's ordering gathers first (0: no tails in use)
     uint64_t last_found = 0;                   // records of the last finished pass: sizes the next pass's ordering grids
@@ -343,7 +333,7 @@ struct havac_ssv_ctx {
     uint64_t first_segment = 0, nsegments = 0; // the shard's segments (bucket numbering)
     int tune_ordering = -1;                    // -1 / 1: bucket ordering, 0: always the radix sort (experiments, tests)
     uint32_t last_order_buckets = 0, last_order_largest = 0; int last_order_path = 0;   // what the last pass's ordering did (tests, tools)
-    unsigned long long* d_count = nullptr;
+    DeviceBuffer<unsigned long long> d_count;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // pass start, kernel start (the model is prepared), kernel end, records ordered
     CellRecord* trace_cells = nullptr; uint32_t trace_row0 = 0, trace_rows = 0, trace_cols = 0; uint64_t trace_col0 = 0;   // per-cell trace window (debugging)
     hipStream_t order_stream = nullptr;        // optional: where finish() orders the records (default: the enqueue's stream)
@@ -391,16 +381,16 @@ extern "C" int havac_ssv_ctx_create(havac_ssv_ctx** out) {
     std::string err;
     auto fail = [&](int code) { havac_ssv_ctx_destroy(c); return code; };
     if (hipGetDevice(&c->device) != hipSuccess) return fail(HAVAC_E_NO_DEVICE);
-    if (hipMalloc(&c->d_count, sizeof(unsigned long long)) != hipSuccess) return fail(HAVAC_E_NOMEM);
-    if (hipMalloc(&c->control, kControlWords * sizeof(uint32_t)) != hipSuccess) return fail(HAVAC_E_NOMEM);
-    if (hipMemset(c->control, 0, kControlWords * sizeof(uint32_t)) != hipSuccess) return fail(HAVAC_E_RUNTIME);
+    if (c->d_count.grow(1) != hipSuccess) return fail(HAVAC_E_NOMEM);
+    if (c->control.grow(kControlWords) != hipSuccess) return fail(HAVAC_E_NOMEM);
+    if (hipMemset(c->control.get(), 0, kControlWords * sizeof(uint32_t)) != hipSuccess) return fail(HAVAC_E_RUNTIME);
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return fail(HAVAC_E_NO_DEVICE);
         c->resident_blocks = prop.multiProcessorCount * kBlocksPerCu;
     }
-    if (hipHostMalloc(&c->h_report, sizeof(PassReport), hipHostMallocDefault) != hipSuccess) return fail(HAVAC_E_NOMEM);
-    std::memset(c->h_report, 0, sizeof(PassReport));
+    if (c->h_report.allocate(1) != hipSuccess) return fail(HAVAC_E_NOMEM);
+    std::memset(c->h_report.get(), 0, sizeof(PassReport));
     // (the ordering kernel's LDS sorter may be asked for 64 KB of dynamic LDS: above the default limit together with its few static words)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ssv_order_finish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLargeBucket * sizeof(uint32_t)));
     for (auto& e : c->ev)
@@ -413,21 +403,6 @@ extern "C" int havac_ssv_ctx_create(havac_ssv_ctx** out) {
 
 extern "C" void havac_ssv_ctx_destroy(havac_ssv_ctx* c) {
     if (!c) return;
-    if (c->rows8) (void)hipFree(c->rows8);
-    if (c->chunk_flags) (void)hipFree(c->chunk_flags);
-    if (c->control) (void)hipFree(c->control);
-    if (c->block_flags) (void)hipFree(c->block_flags);
-    if (c->block_state) (void)hipFree(c->block_state);
-    if (c->tails) (void)hipFree(c->tails);
-    if (c->tail_counts) (void)hipFree(c->tail_counts);
-    if (c->sort_tmp) (void)hipFree(c->sort_tmp);
-    if (c->sort_alt) (void)hipFree(c->sort_alt);
-    if (c->bucket_counts) (void)hipFree(c->bucket_counts);
-    if (c->bucket_offsets) (void)hipFree(c->bucket_offsets);
-    if (c->bucket_chunk_base) (void)hipFree(c->bucket_chunk_base);
-    if (c->bucket_large) (void)hipFree(c->bucket_large);
-    if (c->h_report) (void)hipHostFree(c->h_report);
-    if (c->d_count) (void)hipFree(c->d_count);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -619,19 +594,9 @@ extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, ui
 
     Tiling t = make_tiling(nsymbols, nrows);
     const uint32_t model_words = t.nrows_padded + kModelSlack;   // "row -1", the rows, padding rows
-    if (c->rows8_rows < model_words) {
-        if (c->rows8) (void)hipFree(c->rows8);
-        c->rows8 = nullptr; c->rows8_rows = 0;
-        HIP_TRY(c->err, hipMalloc(&c->rows8, (size_t)model_words * sizeof(uint32_t)));
-        c->rows8_rows = model_words;
-    }
+    if (c->rows8.capacity() < model_words) HIP_TRY(c->err, c->rows8.grow(model_words));
     const uint32_t flag_words = (t.nrows_padded / kChunkRows + 1 + 3) / 4 + 2;     // a byte per chunk; + 2: the kernels load a word ahead
-    if (c->chunk_flag_words < flag_words) {
-        if (c->chunk_flags) (void)hipFree(c->chunk_flags);
-        c->chunk_flags = nullptr; c->chunk_flag_words = 0;
-        HIP_TRY(c->err, hipMalloc(&c->chunk_flags, (size_t)flag_words * sizeof(uint32_t)));
-        c->chunk_flag_words = flag_words;
-    }
+    if (c->chunk_flags.capacity() < flag_words) HIP_TRY(c->err, c->chunk_flags.grow(flag_words));
     uint64_t col_begin, col_end;
     shard_columns(nsymbols, shard_index, shard_count, &col_begin, &col_end);
     uint32_t tb, te;
@@ -678,14 +643,11 @@ extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, ui
         // every tile -- not per tile of the launch (a 3 Gbp genome against a tall model is 1.5 M tiles of
         // which ~9,000 are cut; the counts are cleared on every pass, by ssv_prepare_model)
         const size_t slots_needed = handoff_slots(L);
-        if (c->block_flag_tiles < slots_needed) {
+        if (c->block_flags.capacity() < slots_needed) {
             HIP_TRY(c->err, hipStreamSynchronize(stream));        // an earlier pass on this stream may still use the old buffers
-            if (c->block_flags) (void)hipFree(c->block_flags);
-            if (c->block_state) (void)hipFree(c->block_state);
-            c->block_flags = c->block_state = nullptr; c->block_flag_tiles = c->block_state_tiles = 0;
-            HIP_TRY(c->err, hipMalloc(&c->block_flags, slots_needed * sizeof(uint32_t)));
-            HIP_TRY(c->err, hipMalloc(&c->block_state, slots_needed * (kRegs / 2) * 64 * sizeof(uint32_t)));
-            c->block_flag_tiles = c->block_state_tiles = slots_needed;
+            c->block_flags.reset();                               // (the group's capacity: 0 until every buffer of it is grown)
+            HIP_TRY(c->err, c->block_state.grow(slots_needed * (kRegs / 2) * 64));
+            HIP_TRY(c->err, c->block_flags.grow(slots_needed));
         }
         handoff_words = slots_needed;
     }
@@ -696,23 +658,20 @@ extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, ui
     bool use_tails = te > tb && largest_item_rows <= 512 && (uint64_t)nblocks * kTailSlots * sizeof(uint64_t) <= (128ull << 20);
     if (te > tb && c->tune_block_tails >= 0)      // experiments: 0 = off, 1 = the default rule, 2 = on whatever the height of an item
         use_tails = c->tune_block_tails == 2 ? (uint64_t)nblocks * kTailSlots * sizeof(uint64_t) <= (128ull << 20) : use_tails && c->tune_block_tails != 0;
-    if (use_tails && c->tail_blocks < nblocks) {
+    if (use_tails && c->tail_counts.capacity() < nblocks) {
         HIP_TRY(c->err, hipStreamSynchronize(stream));        // an earlier pass on this stream may still use the old buffers
-        if (c->tails) (void)hipFree(c->tails);
-        if (c->tail_counts) (void)hipFree(c->tail_counts);
-        c->tails = nullptr; c->tail_counts = nullptr; c->tail_blocks = 0;
+        c->tail_counts.reset();                               // (the group's capacity: 0 until every buffer of it is grown)
         const size_t want = (size_t)nblocks + nblocks / 4 + 64;
-        HIP_TRY(c->err, hipMalloc(&c->tails, want * kTailSlots * sizeof(uint64_t)));
-        HIP_TRY(c->err, hipMalloc(&c->tail_counts, want * sizeof(uint32_t)));
-        c->tail_blocks = want;
+        HIP_TRY(c->err, c->tails.grow(want * kTailSlots));
+        HIP_TRY(c->err, c->tail_counts.grow(want));
     }
     // the ordering's second buffer and bucket tables: a first guess here, grown by finish() when the kernel says a pass needs more
     if (hit_capacity) {
         if (int rc2 = ensure_alt(c, std::min<uint64_t>(hit_capacity, 1ull << 22), stream)) return rc2;
         if (int rc2 = ensure_buckets(c, 1u << 16, stream)) return rc2;
     }
-    if (c->order_dirty && c->bucket_counts) {     // an earlier ordering was cut short: its counts cannot be trusted
-        HIP_TRY(c->err, hipMemsetAsync(c->bucket_counts, 0, c->bucket_alloc * sizeof(uint32_t), stream));
+    if (c->order_dirty && c->bucket_counts.get()) {     // an earlier ordering was cut short: its counts cannot be trusted
+        HIP_TRY(c->err, hipMemsetAsync(c->bucket_counts.get(), 0, c->bucket_counts.capacity() * sizeof(uint32_t), stream));
         c->order_dirty = false;
     }
 
@@ -724,36 +683,38 @@ extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, ui
     {
         const uint32_t nflagwords = flag_words;
         const uint32_t threads = std::max(std::max(model_words, nflagwords * 4u), kControlWords);
-        hipLaunchKernelGGL(ssv_prepare_model, dim3((threads + 255) / 256), dim3(256), 0, stream, d_phmm, nrows, c->rows8, model_words,
-                           t.nrows_padded, c->chunk_flags, nflagwords, c->d_count, c->control, kControlWords, c->block_flags, (uint32_t)handoff_words);
+        hipLaunchKernelGGL(ssv_prepare_model, dim3((threads + 255) / 256), dim3(256), 0, stream, d_phmm, nrows, c->rows8.get(), model_words,
+                           t.nrows_padded, c->chunk_flags.get(), nflagwords, c->d_count.get(), c->control.get(), kControlWords, c->block_flags.get(),
+                           (uint32_t)handoff_words);
     }
     HIP_TRY(c->err, hipEventRecord(c->ev[1], stream));
     if (te > tb) {
         SsvRare& R = L;
-        R.hits = d_hits; R.hit_count = c->d_count; R.hit_capacity = hit_capacity;
+        R.hits = d_hits; R.hit_count = c->d_count.get(); R.hit_capacity = hit_capacity;
         R.col_begin = (int64_t)col_begin; R.col_span = col_end - col_begin;
         R.half_tail = (resident_kernel && t.nrows_padded - nrows >= (uint32_t)kChunkRows / 2) ? 1u : 0u;
-        R.abort_flag = d_abort_flag; R.pair_mask = pair_mask; R.tickets = c->control + kControlTickets; R.block_flags = c->block_flags; R.block_state = c->block_state;
-        R.fault = c->control + kControlFault; R.row_bits = row_bits;
-        R.tails = use_tails ? c->tails : nullptr; R.tail_counts = use_tails ? c->tail_counts : nullptr;
+        R.abort_flag = d_abort_flag; R.pair_mask = pair_mask; R.tickets = c->control.get() + kControlTickets; R.block_flags = c->block_flags.get();
+        R.block_state = c->block_state.get();
+        R.fault = c->control.get() + kControlFault; R.row_bits = row_bits;
+        R.tails = use_tails ? c->tails.get() : nullptr; R.tail_counts = use_tails ? c->tail_counts.get() : nullptr;
         R.cells = c->trace_cells; R.cell_row0 = c->trace_row0; R.cell_col0 = (int64_t)c->trace_col0;
         R.cell_rows = c->trace_rows; R.cell_cols = c->trace_cols;
         // (round 5: the chunk flags are handed over with a separator mask too -- a chunk then tests every two steps only where a
         // separator, or the matrix's edge, really lies in the wave's window; the kernel sees the mask in SsvRare::pair_mask)
-        const uint32_t* const safe_chunks = (const uint32_t*)c->chunk_flags;
+        const uint32_t* const safe_chunks = c->chunk_flags.get();
         c->last_resident_kernel = resident_kernel;
         if (c->trace_cells)       // debugging: the same kernel body with the per-cell trace compiled in
             hipLaunchKernelGGL(ssv_diag_kernel_traced, dim3(nblocks), dim3(64 * kWavesPerBlock), 0, stream, R,
-                               d_sequence, (const uint32_t*)c->rows8, safe_chunks, (int64_t)nsymbols, t.nrows_padded);
+                               d_sequence, c->rows8.get(), safe_chunks, (int64_t)nsymbols, t.nrows_padded);
         else if (resident_kernel && pair_mask)
             hipLaunchKernelGGL(ssv_resident_kernel_masked, dim3(nblocks), dim3(64 * kWavesPerBlock), 0, stream, R,
-                               d_sequence, (const uint32_t*)c->rows8, safe_chunks, (int64_t)nsymbols, t.nrows_padded);
+                               d_sequence, c->rows8.get(), safe_chunks, (int64_t)nsymbols, t.nrows_padded);
         else if (resident_kernel)    // short models: the chip's worth of workgroups, tables resident in LDS, every wave walks its run of tiles
             hipLaunchKernelGGL(ssv_resident_kernel, dim3(nblocks), dim3(64 * kWavesPerBlock), 0, stream, R,
-                               d_sequence, (const uint32_t*)c->rows8, safe_chunks, (int64_t)nsymbols, t.nrows_padded);
+                               d_sequence, c->rows8.get(), safe_chunks, (int64_t)nsymbols, t.nrows_padded);
         else
             hipLaunchKernelGGL(ssv_diag_kernel, dim3(nblocks), dim3(64 * kWavesPerBlock), 0, stream, R,
-                               d_sequence, (const uint32_t*)c->rows8, safe_chunks, (int64_t)nsymbols, t.nrows_padded);
+                               d_sequence, c->rows8.get(), safe_chunks, (int64_t)nsymbols, t.nrows_padded);
     }
     HIP_TRY(c->err, hipEventRecord(c->ev[2], stream));
     // The third and last launch of the pass, the ordering (hit_order.hip.h: the count is read on the device, the tails where they
@@ -781,15 +742,9 @@ static int sort_run(havac_ssv_ctx* c, uint64_t* keys, uint64_t* alt, uint64_t co
     // `count` keys in `keys` -> sorted in `alt`
     size_t need = 0;
     HIP_TRY(c->err, rocprim::radix_sort_keys<hit_sort_config>(nullptr, need, keys, alt, (size_t)count, 0, key_bits, stream));
-    if (c->sort_tmp_bytes < need) {
-        HIP_TRY(c->err, hipStreamSynchronize(stream));        // an earlier run on this stream may still use the old one
-        if (c->sort_tmp) (void)hipFree(c->sort_tmp);
-        c->sort_tmp = nullptr; c->sort_tmp_bytes = 0;
-        HIP_TRY(c->err, hipMalloc(&c->sort_tmp, need + need / 4));
-        c->sort_tmp_bytes = need + need / 4;
-    }
-    size_t bytes = c->sort_tmp_bytes;
-    HIP_TRY(c->err, rocprim::radix_sort_keys<hit_sort_config>(c->sort_tmp, bytes, keys, alt, (size_t)count, 0, key_bits, stream));
+    if (c->sort_tmp.capacity() < need) HIP_TRY(c->err, c->sort_tmp.grow(need + need / 4, stream));     // (an earlier run on this stream may still use the old one)
+    size_t bytes = c->sort_tmp.capacity();
+    HIP_TRY(c->err, rocprim::radix_sort_keys<hit_sort_config>(c->sort_tmp.get(), bytes, keys, alt, (size_t)count, 0, key_bits, stream));
     return HAVAC_OK;
 }
 
@@ -797,41 +752,33 @@ static int sort_keys(havac_ssv_ctx* c, uint64_t* keys, uint64_t count, hipStream
     if (count < 2) return HAVAC_OK;
     if (int rc = ensure_alt(c, count, stream)) return rc;
     // (rocPRIM orders more than 2^32 keys in one call: 4.5e9 checked, tools/big_sort_check.py)
-    int rc = sort_run(c, keys, c->sort_alt, count, stream, key_bits);
+    int rc = sort_run(c, keys, c->sort_alt.get(), count, stream, key_bits);
     if (rc) return rc;
-    HIP_TRY(c->err, hipMemcpyAsync(keys, c->sort_alt, count * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(c->err, hipMemcpyAsync(keys, c->sort_alt.get(), count * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
     return HAVAC_OK;
 }
 
 // ---- ordering ------------------------------------------------------------------------------------------------------------
 static int ensure_alt(havac_ssv_ctx* c, uint64_t count, hipStream_t stream) {
-    if (c->sort_alt_count >= count) return HAVAC_OK;
-    HIP_TRY(c->err, hipStreamSynchronize(stream));            // an earlier pass on this stream may still use the old one
-    if (c->sort_alt) (void)hipFree(c->sort_alt);
-    c->sort_alt = nullptr; c->sort_alt_count = 0;
-    const size_t want = (size_t)count + count / 4 + 1024;
-    HIP_TRY(c->err, hipMalloc(&c->sort_alt, want * sizeof(uint64_t)));
-    c->sort_alt_count = want;
+    if (c->sort_alt.capacity() >= count) return HAVAC_OK;
+    HIP_TRY(c->err, c->sort_alt.grow((size_t)count + count / 4 + 1024, stream));      // (an earlier pass on this stream may still use the old one)
     return HAVAC_OK;
 }
 
 static int ensure_buckets(havac_ssv_ctx* c, uint32_t nbuckets, hipStream_t stream) {
-    if (c->bucket_alloc >= nbuckets) return HAVAC_OK;
-    HIP_TRY(c->err, hipStreamSynchronize(stream));
-    if (c->bucket_counts) (void)hipFree(c->bucket_counts);
-    if (c->bucket_offsets) (void)hipFree(c->bucket_offsets);
-    if (c->bucket_chunk_base) (void)hipFree(c->bucket_chunk_base);
-    if (c->bucket_large) (void)hipFree(c->bucket_large);
-    c->bucket_counts = nullptr; c->bucket_offsets = nullptr; c->bucket_chunk_base = nullptr; c->bucket_large = nullptr; c->bucket_alloc = 0;
+    if (c->bucket_counts.capacity() >= nbuckets) return HAVAC_OK;
+    HIP_TRY(c->err, hipStreamSynchronize(stream));            // an earlier pass on this stream may still use the old tables
+    c->bucket_counts.reset();                                 // (the tables' capacity: 0 until all four are grown and the counts zeroed)
     const size_t want = (size_t)nbuckets + nbuckets / 4 + 1024;
-    HIP_TRY(c->err, hipMalloc(&c->bucket_counts, want * sizeof(uint32_t)));
-    HIP_TRY(c->err, hipMalloc(&c->bucket_offsets, want * sizeof(uint32_t)));
-    HIP_TRY(c->err, hipMalloc(&c->bucket_chunk_base, (want / kScanChunk + 2) * sizeof(uint64_t)));
-    HIP_TRY(c->err, hipMalloc(&c->bucket_large, want * sizeof(uint32_t)));
+    HIP_TRY(c->err, c->bucket_offsets.grow(want));
+    HIP_TRY(c->err, c->bucket_chunk_base.grow(want / kScanChunk + 2));
+    HIP_TRY(c->err, c->bucket_large.grow(want));
+    DeviceBuffer<uint32_t> counts;
+    HIP_TRY(c->err, counts.grow(want));
     // once: every pass leaves the counts at zero.  (On the pass's own stream: a null-stream hipMemset is not ordered against a
     // non-blocking stream, and the kernels would race with it.)
-    HIP_TRY(c->err, hipMemsetAsync(c->bucket_counts, 0, want * sizeof(uint32_t), stream));
-    c->bucket_alloc = want;
+    HIP_TRY(c->err, hipMemsetAsync(counts.get(), 0, want * sizeof(uint32_t), stream));
+    c->bucket_counts = std::move(counts);
     return HAVAC_OK;
 }
 
@@ -852,24 +799,24 @@ static int order_by_radix_sort(havac_ssv_ctx* c, uint64_t* d_hits, uint64_t coun
 static int launch_ordering(havac_ssv_ctx* c, unsigned seg_bits) {
     const hipStream_t after = c->order_stream ? c->order_stream : c->stream;
     OrderPass& a = c->order_args;
-    a.hits = c->d_hits; a.alt = c->sort_alt; a.alt_capacity = c->sort_alt_count; a.capacity = c->hit_capacity;
-    a.hit_count = c->d_count;
-    a.counts = c->bucket_counts; a.offsets = c->bucket_offsets; a.chunk_base = c->bucket_chunk_base; a.large_list = c->bucket_large;
-    a.max_buckets = (uint32_t)std::min<size_t>(c->bucket_alloc, 1u << 27);
-    a.state = reinterpret_cast<OrderState*>(c->control + kControlOrderState);
-    a.host = c->h_report; a.ssv_fault = c->control + kControlFault;
+    a.hits = c->d_hits; a.alt = c->sort_alt.get(); a.alt_capacity = c->sort_alt.capacity(); a.capacity = c->hit_capacity;
+    a.hit_count = c->d_count.get();
+    a.counts = c->bucket_counts.get(); a.offsets = c->bucket_offsets.get(); a.chunk_base = c->bucket_chunk_base.get(); a.large_list = c->bucket_large.get();
+    a.max_buckets = (uint32_t)std::min<size_t>(c->bucket_counts.capacity(), 1u << 27);
+    a.state = reinterpret_cast<OrderState*>(c->control.get() + kControlOrderState);
+    a.host = c->h_report.get(); a.ssv_fault = c->control.get() + kControlFault;
     a.row_bits = c->row_bits; a.seg_bits = seg_bits; a.large_capacity = c->large_capacity;
-    a.generic = (c->tune_ordering == 0 || c->hit_capacity == 0 || !c->sort_alt || !c->bucket_counts) ? 1u : 0u;
+    a.generic = (c->tune_ordering == 0 || c->hit_capacity == 0 || !c->sort_alt.get() || !c->bucket_counts.get()) ? 1u : 0u;
     a.first_segment = c->first_segment; a.nsegments = c->nsegments;
     // what the blocks left in their tails joins the queue first (short items only; ssv_kernels.hip.h, "block tails")
     if (c->order_tail_blocks && !c->tails_gathered) {
-        hipLaunchKernelGGL(ssv_gather_tails, dim3((c->order_tail_blocks + kGatherBlocks - 1) / kGatherBlocks), dim3(256), 0, after, (const uint64_t*)c->tails,
-                           (const uint32_t*)c->tail_counts, c->order_tail_blocks, c->d_hits, c->d_count, c->hit_capacity);
+        hipLaunchKernelGGL(ssv_gather_tails, dim3((c->order_tail_blocks + kGatherBlocks - 1) / kGatherBlocks), dim3(256), 0, after, (const uint64_t*)c->tails.get(),
+                           (const uint32_t*)c->tail_counts.get(), c->order_tail_blocks, c->d_hits, c->d_count.get(), c->hit_capacity);
         c->tails_gathered = true;
     }
     const size_t scan_bytes = (size_t)(kScanChunk + 64u) * sizeof(uint32_t), large_bytes = (size_t)c->large_capacity * sizeof(uint32_t);
     const int cus = c->resident_blocks / kBlocksPerCu;
-    c->h_report->status = kOrderNone;
+    c->h_report.get()->status = kOrderNone;
     // Grids: the kernels walk the list in strides of their grid, so any size is right; the count is not known here, the LAST
     // pass's is (same context, usually the same workload): enough workgroups for a quarter more than that, within bounds --
     // a grid whose workgroups mostly have nothing to do still costs its dispatch (a 64-row model x 100 Mbp orders 50,000 records).
@@ -905,7 +852,7 @@ extern "C" int havac_ssv_finish_end(havac_ssv_ctx* c, uint64_t* hit_count_out) {
     c->pending = false;
     HIP_TRY(c->err, hipSetDevice(c->device));
     const hipStream_t after = c->order_stream ? c->order_stream : c->stream;
-    const PassReport* const rep = c->h_report;
+    const PassReport* const rep = c->h_report.get();
     c->last_order_path = 1; c->last_order_buckets = 0; c->last_order_largest = 0;
     for (int attempt = 0;; attempt++) {
         if (hipError_t e = hipEventSynchronize(c->ev[3]); e != hipSuccess) { c->order_dirty = true; c->err = hip_msg("hipEventSynchronize", e); return HAVAC_E_RUNTIME; }
@@ -921,9 +868,9 @@ extern "C" int havac_ssv_finish_end(havac_ssv_ctx* c, uint64_t* hit_count_out) {
         if (status == kOrderRetry && attempt < 4) {
             // a buffer of the context was too small for this pass; nothing was moved: grow it, clear the barrier words, again
             if (int rc = ensure_alt(c, rep->need_alt, after)) return rc;
-            if (rep->need_buckets == 0 || rep->need_buckets > c->bucket_alloc) { if (int rc = ensure_buckets(c, std::max<uint32_t>(rep->need_buckets, 1u << 16), after)) return rc; }
+            if (rep->need_buckets == 0 || rep->need_buckets > c->bucket_counts.capacity()) { if (int rc = ensure_buckets(c, std::max<uint32_t>(rep->need_buckets, 1u << 16), after)) return rc; }
             if (rep->need_large > c->large_capacity) { uint32_t cap = c->large_capacity; while (cap < rep->need_large && cap < kLargeBucket) cap *= 2; c->large_capacity = cap; }
-            HIP_TRY(c->err, hipMemsetAsync(c->control + kControlOrderState, 0, sizeof(OrderState), after));
+            HIP_TRY(c->err, hipMemsetAsync(c->control.get() + kControlOrderState, 0, sizeof(OrderState), after));
             unsigned seg_bits = c->key_bits - 14 - c->row_bits;
             if (int rc = launch_ordering(c, seg_bits)) return rc;
             continue;
@@ -931,7 +878,7 @@ extern "C" int havac_ssv_finish_end(havac_ssv_ctx* c, uint64_t* hit_count_out) {
         if (status == kOrderGeneric) {
             // the generic path: what the blocks left in their tails joins the queue, then radix sort + key -> record
             c->last_order_path = c->tune_ordering == 0 ? 0 : 2;
-            if (rep->oversized & 2u) HIP_TRY(c->err, hipMemsetAsync(c->bucket_counts, 0, c->bucket_alloc * sizeof(uint32_t), after));
+            if (rep->oversized & 2u) HIP_TRY(c->err, hipMemsetAsync(c->bucket_counts.get(), 0, c->bucket_counts.capacity() * sizeof(uint32_t), after));
             if (int rc = order_by_radix_sort(c, c->d_hits, c->found, after)) return rc;
             HIP_TRY(c->err, hipEventRecord(c->ev[3], after));
             HIP_TRY(c->err, hipEventSynchronize(c->ev[3]));
@@ -1006,23 +953,20 @@ extern "C" int havac_ssv_check_order(const uint64_t* d_records, uint64_t count, 
     const hipStream_t stream = (hipStream_t)hip_stream;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return HAVAC_E_NO_DEVICE;
-    uint64_t* d_table = nullptr; OrderReport* d_report = nullptr;
+    DeviceBuffer<uint64_t> d_table; DeviceBuffer<OrderReport> d_report;
     OrderReport report{count, 0, ~0ull, 0, ~0ull};
-    hipError_t e = hipMalloc(&d_table, table.size() * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&d_report, sizeof(OrderReport));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_report, &report, sizeof report, hipMemcpyHostToDevice, stream);
+    hipError_t e = d_table.copy_from(table.data(), table.size(), stream);
+    if (e == hipSuccess) e = d_report.copy_from(&report, 1, stream);
     if (e == hipSuccess && count) {
         // grid-stride: a dispatch counts its work-items in 32 bits, the list may hold more records than that
         const unsigned blocks = (unsigned)std::min<uint64_t>((count + 255) / 256, 1u << 16);
-        hipLaunchKernelGGL(ssv_check_order, dim3(blocks), dim3(256), 0, stream, d_records, count, (const uint64_t*)d_table,
-                           (const uint64_t*)(d_table + nranks + 1), (const uint64_t*)(d_table + 2 * (size_t)nranks + 1), nranks, d_report);
+        hipLaunchKernelGGL(ssv_check_order, dim3(blocks), dim3(256), 0, stream, d_records, count, (const uint64_t*)d_table.get(),
+                           (const uint64_t*)(d_table.get() + nranks + 1), (const uint64_t*)(d_table.get() + 2 * (size_t)nranks + 1), nranks,
+                           d_report.get());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&report, d_report, sizeof report, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&report, d_report.get(), sizeof report, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (d_table) (void)hipFree(d_table);
-    if (d_report) (void)hipFree(d_report);
     if (e != hipSuccess) return e == hipErrorOutOfMemory ? HAVAC_E_NOMEM : HAVAC_E_RUNTIME;
     out->records = report.records; out->out_of_order = report.out_of_order; out->first_out_of_order = report.first_out_of_order;
     out->out_of_span = report.out_of_span; out->first_out_of_span = report.first_out_of_span;
@@ -1042,20 +986,25 @@ extern "C" int havac_ssv_last_ms(havac_ssv_ctx* c, float* ssv_kernel_ms, float* 
 // One handle drives one GPU (havac_dev_create) or several (havac_dev_create_multi): every GPU of the handle holds the
 // whole sequence and model and computes one column shard (see shard_columns); because shards are whole segments, the
 // GPUs' ordered hit lists concatenated in shard order are the ordered whole.
+// (move-only: the parts of a handle are made by one resize; its device memory is freed with its device current, see the destructor)
 struct DevicePart {
     int device = 0;
     hipStream_t stream = nullptr;       // uploads, packing kernels; a run starts behind what this stream holds
     havac_pipe* pipe = nullptr;         // the runs of this GPU: `depth` slots (context, hit buffer, ordering stream each; havac_pipe.hip)
-    uint8_t* d_seq = nullptr; uint64_t seq_alloc = 0;
-    int8_t* d_phmm = nullptr; uint64_t phmm_alloc = 0;
-    uint8_t* d_mask = nullptr; uint64_t mask_alloc = 0;   // separator bitmap, optional
+    DeviceBuffer<uint8_t> d_seq;
+    DeviceBuffer<int8_t> d_phmm;
+    DeviceBuffer<uint8_t> d_mask;       // separator bitmap, optional
     uint64_t win_first = 0, win_columns = 0;              // d_seq / d_mask hold these columns only (0, 0: all); see upload_columns
-    uint32_t* d_abort = nullptr;        // kMaxDepth device words the kernels poll (cache-bypassing loads), one per run in flight
+    DeviceBuffer<uint32_t> d_abort;     // kMaxDepth device words the kernels poll (cache-bypassing loads), one per run in flight
     hipStream_t abort_stream = nullptr; // abort() writes the words from here while the kernels run
     // text staging of havac_dev_write_sequence_chars (allocated on first use)
-    char* d_chars[2] = {nullptr, nullptr};
+    DeviceBuffer<char> d_chars[2];
     hipEvent_t chars_copied[2] = {nullptr, nullptr}, chars_packed[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr;
+
+    DevicePart() = default;
+    DevicePart(DevicePart&&) = default;
+    ~DevicePart() { (void)hipSetDevice(device); }      // (the members are destroyed after this body: on this part's device)
 };
 
 // One run of the handle: havac_dev_run_async opens it, havac_dev_wait / _state / _abort finish it, havac_dev_num_hits / _read_hits
@@ -1136,8 +1085,8 @@ extern "C" int havac_dev_create_multi(const uint32_t* device_indices, uint32_t n
         if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(HAVAC_E_NO_DEVICE);   // the code object is gfx950 only
         if (hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking) != hipSuccess) return fail(HAVAC_E_RUNTIME);
         if (hipStreamCreateWithFlags(&p.abort_stream, hipStreamNonBlocking) != hipSuccess) return fail(HAVAC_E_RUNTIME);
-        if (hipMalloc(&p.d_abort, kMaxDepth * sizeof(uint32_t)) != hipSuccess) return fail(HAVAC_E_NOMEM);
-        if (hipMemset(p.d_abort, 0, kMaxDepth * sizeof(uint32_t)) != hipSuccess) return fail(HAVAC_E_RUNTIME);
+        if (p.d_abort.grow(kMaxDepth) != hipSuccess) return fail(HAVAC_E_NOMEM);
+        if (hipMemset(p.d_abort.get(), 0, kMaxDepth * sizeof(uint32_t)) != hipSuccess) return fail(HAVAC_E_RUNTIME);
     }
     if (dev_make_pipes(d, 1, kDefaultHitCapacity) != HAVAC_OK) return fail(HAVAC_E_NOMEM);
     *out = d;
@@ -1154,12 +1103,7 @@ extern "C" void havac_dev_destroy(havac_dev* d) {
         (void)hipSetDevice(p.device);
         if (p.stream) (void)hipStreamSynchronize(p.stream);
         if (p.pipe) havac_pipe_destroy(p.pipe);
-        if (p.d_seq) (void)hipFree(p.d_seq);
-        if (p.d_phmm) (void)hipFree(p.d_phmm);
-        if (p.d_mask) (void)hipFree(p.d_mask);
-        if (p.d_abort) (void)hipFree(p.d_abort);
         for (int k = 0; k < 2; k++) {
-            if (p.d_chars[k]) (void)hipFree(p.d_chars[k]);
             if (p.chars_copied[k]) (void)hipEventDestroy(p.chars_copied[k]);
             if (p.chars_packed[k]) (void)hipEventDestroy(p.chars_packed[k]);
         }
@@ -1167,7 +1111,7 @@ extern "C" void havac_dev_destroy(havac_dev* d) {
         if (p.abort_stream) (void)hipStreamDestroy(p.abort_stream);
         if (p.stream) (void)hipStreamDestroy(p.stream);
     }
-    delete d;
+    delete d;          // (the parts' device memory: ~DevicePart)
 }
 
 extern "C" const char* havac_dev_last_error(havac_dev* d) { return d ? d->err.c_str() : "null handle"; }
@@ -1215,40 +1159,32 @@ static int wait_inputs_read(havac_dev* d, bool sequence_too) {
     return HAVAC_OK;
 }
 
-// copies a host buffer to the same-named device buffer of every GPU of the handle
-// Several GPUs behind the handle: the caller's pages are locked for the duration of the call, so that the per-GPU copies are
-// truly asynchronous and cross PCIe side by side (from pageable memory every hipMemcpyAsync is staged by the runtime and the
-// GPUs load one after the other: invisible at C4's 31 MB per GPU, eight times the time at the reference's 4 GiB limit).
-// One GPU: nothing to overlap, nothing is locked.  If the pages cannot be locked the copies still work, staged.
-struct LockedSource {
-    void* p = nullptr;
-    const havac_dev* dev;
-    LockedSource(const havac_dev* d, const void* src, uint64_t nbytes) : dev(d) {
-        if (d->parts.size() > 1 && nbytes >= (1u << 20)) {
-            if (hipHostRegister(const_cast<void*>(src), nbytes, hipHostRegisterDefault) == hipSuccess) p = const_cast<void*>(src);
-            else (void)hipGetLastError();
+// The caller's pages locked while the GPUs of the handle copy from them (PageLock), so that the copies are truly asynchronous; if
+// they cannot be locked the copies still work, staged.  Before the pages are unlocked every GPU's copies from them have drained
+// (on an early error return some may still be in flight).
+static auto lock_source(const havac_dev* d, const void* src, uint64_t nbytes, bool want) {
+    return PageLock(src, nbytes, want, [d] {
+        for (const DevicePart& part : d->parts) {
+            if (hipSetDevice(part.device) != hipSuccess) continue;
+            if (part.stream) (void)hipStreamSynchronize(part.stream);
+            if (part.copy_stream) (void)hipStreamSynchronize(part.copy_stream);
         }
-    }
-    ~LockedSource() {
-        if (!p) return;
-        // on an early error return some GPUs' copies from these pages may still be in flight: drained before the pages are unlocked
-        for (const DevicePart& part : dev->parts)
-            if (part.stream && hipSetDevice(part.device) == hipSuccess) (void)hipStreamSynchronize(part.stream);
-        (void)hipHostUnregister(p);
-    }
-};
+    });
+}
+
+// copies a host buffer to the same-named device buffer of every GPU of the handle
+// Several GPUs behind the handle: the caller's pages are locked for the duration of the call, so that the per-GPU copies
+// cross PCIe side by side (from pageable memory every hipMemcpyAsync is staged by the runtime and the GPUs load one after the
+// other: invisible at C4's 31 MB per GPU, eight times the time at the reference's 4 GiB limit).  One GPU: nothing to overlap,
+// nothing is locked.
+static bool worth_locking(const havac_dev* d, uint64_t nbytes) { return d->parts.size() > 1 && nbytes >= (1u << 20); }
 template <typename T>
-static int upload(havac_dev* d, T* DevicePart::*buf, uint64_t DevicePart::*alloc, const void* src, uint64_t nbytes) {
-    const LockedSource locked(d, src, nbytes);
+static int upload(havac_dev* d, DeviceBuffer<T> DevicePart::*buf, const void* src, uint64_t nbytes) {
+    const auto locked = lock_source(d, src, nbytes, worth_locking(d, nbytes));
     for (DevicePart& p : d->parts) {
         HIP_TRY(d->err, hipSetDevice(p.device));
-        if (p.*alloc < nbytes) {
-            if (p.*buf) (void)hipFree(p.*buf);
-            p.*buf = nullptr; p.*alloc = 0;
-            HIP_TRY(d->err, hipMalloc(&(p.*buf), nbytes));
-            p.*alloc = nbytes;
-        }
-        HIP_TRY(d->err, hipMemcpyAsync(p.*buf, src, nbytes, hipMemcpyHostToDevice, p.stream));
+        if ((p.*buf).capacity() < nbytes) HIP_TRY(d->err, (p.*buf).grow(nbytes));
+        HIP_TRY(d->err, hipMemcpyAsync((p.*buf).get(), src, nbytes, hipMemcpyHostToDevice, p.stream));
     }
     for (DevicePart& p : d->parts) {
         HIP_TRY(d->err, hipSetDevice(p.device));
@@ -1272,22 +1208,16 @@ static void part_window(const havac_dev* d, uint64_t ncolumns, uint32_t part, ui
     *first = wf; *columns = we - wf;
 }
 template <typename T>
-static int upload_columns(havac_dev* d, T* DevicePart::*buf, uint64_t DevicePart::*alloc, const uint8_t* src, uint64_t ncolumns,
-                          uint32_t columns_per_byte) {
-    const LockedSource locked(d, src, ncolumns / columns_per_byte);
+static int upload_columns(havac_dev* d, DeviceBuffer<T> DevicePart::*buf, const uint8_t* src, uint64_t ncolumns, uint32_t columns_per_byte) {
+    const auto locked = lock_source(d, src, ncolumns / columns_per_byte, worth_locking(d, ncolumns / columns_per_byte));
     for (uint32_t i = 0; i < d->parts.size(); i++) {
         DevicePart& p = d->parts[i];
         HIP_TRY(d->err, hipSetDevice(p.device));
         part_window(d, ncolumns, i, &p.win_first, &p.win_columns);
         const uint64_t first = p.win_first, columns = p.win_columns ? p.win_columns : ncolumns;
         const uint64_t nbytes = columns / columns_per_byte;
-        if (p.*alloc < nbytes) {
-            if (p.*buf) (void)hipFree(p.*buf);
-            p.*buf = nullptr; p.*alloc = 0;
-            HIP_TRY(d->err, hipMalloc(&(p.*buf), nbytes));
-            p.*alloc = nbytes;
-        }
-        HIP_TRY(d->err, hipMemcpyAsync(p.*buf, src + first / columns_per_byte, nbytes, hipMemcpyHostToDevice, p.stream));
+        if ((p.*buf).capacity() < nbytes) HIP_TRY(d->err, (p.*buf).grow(nbytes));
+        HIP_TRY(d->err, hipMemcpyAsync((p.*buf).get(), src + first / columns_per_byte, nbytes, hipMemcpyHostToDevice, p.stream));
     }
     for (DevicePart& p : d->parts) {
         HIP_TRY(d->err, hipSetDevice(p.device));
@@ -1314,7 +1244,7 @@ extern "C" int havac_dev_write_sequence(havac_dev* d, const uint8_t* packed, uin
     d->seq_bytes = nbytes;
     d->mask_bytes = 0;                       // a new sequence has no separators until a mask is written for it
     if (nbytes == 0) return HAVAC_OK;
-    return upload_columns(d, &DevicePart::d_seq, &DevicePart::seq_alloc, packed, nbytes * 4, 4);
+    return upload_columns(d, &DevicePart::d_seq, packed, nbytes * 4, 4);
 }
 
 // SURVEY.md section 8 row f4.  Text in, packed on the GPU.  Per GPU: two staging buffers of kCharChunk characters;
@@ -1341,73 +1271,59 @@ extern "C" int havac_dev_write_sequence_chars(havac_dev* d, const char* chars, u
     d->mask_bytes = 0;
     whole_copies(d);
     if (nbytes == 0) return HAVAC_OK;
-    // page-locked source: the chunk copies then run at PCIe speed and truly asynchronously; if the pages cannot be
-    // locked the copies still work, through the runtime's own staging
-    const bool locked = hipHostRegister(const_cast<char*>(chars), nchars, hipHostRegisterDefault) == hipSuccess;
-    if (!locked) (void)hipGetLastError();
-    int rc = HAVAC_OK;
-    auto run = [&]() -> int {
-        for (DevicePart& p : d->parts) {
-            HIP_TRY(d->err, hipSetDevice(p.device));
-            if (p.seq_alloc < nbytes) {
-                if (p.d_seq) (void)hipFree(p.d_seq);
-                p.d_seq = nullptr; p.seq_alloc = 0;
-                HIP_TRY(d->err, hipMalloc(&p.d_seq, nbytes));
-                p.seq_alloc = nbytes;
+    // page-locked source: the chunk copies then run at PCIe speed and truly asynchronously
+    const auto locked = lock_source(d, chars, nchars, true);
+    for (DevicePart& p : d->parts) {
+        HIP_TRY(d->err, hipSetDevice(p.device));
+        if (p.d_seq.capacity() < nbytes) HIP_TRY(d->err, p.d_seq.grow(nbytes));
+        if (!p.copy_stream) {         // (made last: a set-up that an error cut short is completed by the next call)
+            for (int k = 0; k < 2; k++) {
+                if (!p.d_chars[k].get()) HIP_TRY(d->err, p.d_chars[k].grow(kCharChunk));
+                if (!p.chars_copied[k]) HIP_TRY(d->err, hipEventCreateWithFlags(&p.chars_copied[k], hipEventDisableTiming));
+                if (!p.chars_packed[k]) HIP_TRY(d->err, hipEventCreateWithFlags(&p.chars_packed[k], hipEventDisableTiming));
             }
-            if (!p.d_chars[0]) {
-                for (int k = 0; k < 2; k++) {
-                    HIP_TRY(d->err, hipMalloc(&p.d_chars[k], kCharChunk));
-                    HIP_TRY(d->err, hipEventCreateWithFlags(&p.chars_copied[k], hipEventDisableTiming));
-                    HIP_TRY(d->err, hipEventCreateWithFlags(&p.chars_packed[k], hipEventDisableTiming));
-                }
-                HIP_TRY(d->err, hipStreamCreateWithFlags(&p.copy_stream, hipStreamNonBlocking));
-            }
-            uint32_t* const packed = reinterpret_cast<uint32_t*>(p.d_seq);
-            uint64_t chunk = 0;
-            for (uint64_t off = 0; off < ncolumns; off += kCharChunk, chunk++) {
-                const int k = (int)(chunk & 1);
-                const uint64_t have = off < nchars ? std::min(kCharChunk, nchars - off) : 0;     // characters in this chunk
-                const uint64_t upto = std::min(off + kCharChunk, ncolumns);                      // columns it covers
-                if (chunk >= 2) HIP_TRY(d->err, hipStreamWaitEvent(p.copy_stream, p.chars_packed[k], 0));
-                if (have) HIP_TRY(d->err, hipMemcpyAsync(p.d_chars[k], chars + off, have, hipMemcpyHostToDevice, p.copy_stream));
-                HIP_TRY(d->err, hipEventRecord(p.chars_copied[k], p.copy_stream));
-                HIP_TRY(d->err, hipStreamWaitEvent(p.stream, p.chars_copied[k], 0));
-                const uint64_t words = (upto - off) / 16;
-                hipLaunchKernelGGL(ssv_pack_chars, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, p.stream,
-                                   reinterpret_cast<const uint8_t*>(p.d_chars[k]), off, nchars, upto, packed);
-                HIP_TRY(d->err, hipEventRecord(p.chars_packed[k], p.stream));
-            }
-            if (npatches) {
-                uint64_t* d_cols = nullptr; uint8_t* d_syms = nullptr;
-                HIP_TRY(d->err, hipMalloc(&d_cols, npatches * sizeof(uint64_t)));
-                if (hipMalloc(&d_syms, npatches) != hipSuccess) { (void)hipFree(d_cols); d->err = "out of device memory"; return HAVAC_E_NOMEM; }
-                hipError_t e = hipMemcpyAsync(d_cols, patch_columns, npatches * sizeof(uint64_t), hipMemcpyHostToDevice, p.stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(d_syms, patch_symbols, npatches, hipMemcpyHostToDevice, p.stream);
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(ssv_patch_symbols, dim3((unsigned)((npatches + 255) / 256)), dim3(256), 0, p.stream,
-                                       d_cols, d_syms, npatches, packed);
-                    e = hipStreamSynchronize(p.stream);
-                }
-                (void)hipFree(d_cols); (void)hipFree(d_syms);
-                if (e != hipSuccess) { d->err = hip_msg("patching the sequence", e); return HAVAC_E_RUNTIME; }
-            }
+            HIP_TRY(d->err, hipStreamCreateWithFlags(&p.copy_stream, hipStreamNonBlocking));
         }
-        for (DevicePart& p : d->parts) {
-            HIP_TRY(d->err, hipSetDevice(p.device));
-            HIP_TRY(d->err, hipStreamSynchronize(p.stream));
-            HIP_TRY(d->err, hipGetLastError());
+        uint32_t* const packed = reinterpret_cast<uint32_t*>(p.d_seq.get());
+        uint64_t chunk = 0;
+        for (uint64_t off = 0; off < ncolumns; off += kCharChunk, chunk++) {
+            const int k = (int)(chunk & 1);
+            const uint64_t have = off < nchars ? std::min(kCharChunk, nchars - off) : 0;     // characters in this chunk
+            const uint64_t upto = std::min(off + kCharChunk, ncolumns);                      // columns it covers
+            if (chunk >= 2) HIP_TRY(d->err, hipStreamWaitEvent(p.copy_stream, p.chars_packed[k], 0));
+            if (have) HIP_TRY(d->err, hipMemcpyAsync(p.d_chars[k].get(), chars + off, have, hipMemcpyHostToDevice, p.copy_stream));
+            HIP_TRY(d->err, hipEventRecord(p.chars_copied[k], p.copy_stream));
+            HIP_TRY(d->err, hipStreamWaitEvent(p.stream, p.chars_copied[k], 0));
+            const uint64_t words = (upto - off) / 16;
+            hipLaunchKernelGGL(ssv_pack_chars, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, p.stream,
+                               reinterpret_cast<const uint8_t*>(p.d_chars[k].get()), off, nchars, upto, packed);
+            HIP_TRY(d->err, hipEventRecord(p.chars_packed[k], p.stream));
         }
-        return HAVAC_OK;
-    };
-    rc = run();
-    if (locked) (void)hipHostUnregister(const_cast<char*>(chars));
-    return rc;
+        if (npatches) {
+            DeviceBuffer<uint64_t> d_cols; DeviceBuffer<uint8_t> d_syms;
+            HIP_TRY(d->err, d_cols.grow(npatches));
+            if (d_syms.grow(npatches) != hipSuccess) { d->err = "out of device memory"; return HAVAC_E_NOMEM; }
+            hipError_t e = hipMemcpyAsync(d_cols.get(), patch_columns, npatches * sizeof(uint64_t), hipMemcpyHostToDevice, p.stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_syms.get(), patch_symbols, npatches, hipMemcpyHostToDevice, p.stream);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(ssv_patch_symbols, dim3((unsigned)((npatches + 255) / 256)), dim3(256), 0, p.stream,
+                                   d_cols.get(), d_syms.get(), npatches, packed);
+                e = hipStreamSynchronize(p.stream);
+            }
+            if (e != hipSuccess) { d->err = hip_msg("patching the sequence", e); return HAVAC_E_RUNTIME; }
+        }
+    }
+    for (DevicePart& p : d->parts) {
+        HIP_TRY(d->err, hipSetDevice(p.device));
+        HIP_TRY(d->err, hipStreamSynchronize(p.stream));
+        HIP_TRY(d->err, hipGetLastError());
+    }
+    return HAVAC_OK;
 }
 
 // the first `nbytes` of a per-column buffer as the handle's GPUs hold it: every GPU contributes its own columns
 template <typename T>
-static int read_columns(havac_dev* d, T* DevicePart::*buf, uint8_t* out, uint64_t nbytes, uint64_t ncolumns, uint32_t columns_per_byte) {
+static int read_columns(havac_dev* d, DeviceBuffer<T> DevicePart::*buf, uint8_t* out, uint64_t nbytes, uint64_t ncolumns, uint32_t columns_per_byte) {
     const uint32_t nparts = (uint32_t)d->parts.size();
     for (uint32_t i = 0; i < nparts; i++) {
         DevicePart& p = d->parts[i];
@@ -1422,7 +1338,7 @@ static int read_columns(havac_dev* d, T* DevicePart::*buf, uint8_t* out, uint64_
         const uint64_t from = b / columns_per_byte, to = std::min(e / columns_per_byte, nbytes);
         if (from >= to) continue;
         HIP_TRY(d->err, hipSetDevice(p.device));
-        HIP_TRY(d->err, hipMemcpy(out + from, p.*buf + (from - p.win_first / columns_per_byte), to - from, hipMemcpyDeviceToHost));
+        HIP_TRY(d->err, hipMemcpy(out + from, (p.*buf).get() + (from - p.win_first / columns_per_byte), to - from, hipMemcpyDeviceToHost));
     }
     return HAVAC_OK;
 }
@@ -1440,19 +1356,6 @@ extern "C" int havac_dev_read_separator_mask(havac_dev* d, uint8_t* out, uint64_
     if (nbytes == 0) return HAVAC_OK;
     return read_columns(d, &DevicePart::d_mask, out, nbytes, d->seq_bytes * 4, 16);
 }
-
-namespace {
-// host array -> a device array that lives until the caller frees it
-template <typename T>
-int to_device(std::string& err, const T* src, size_t n, T** out, hipStream_t stream) {
-    *out = nullptr;
-    if (n == 0) return HAVAC_OK;
-    HIP_TRY(err, hipMalloc(out, n * sizeof(T)));
-    hipError_t e = hipMemcpyAsync(*out, src, n * sizeof(T), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) { (void)hipFree(*out); *out = nullptr; err = hip_msg("hipMemcpyAsync", e); return HAVAC_E_RUNTIME; }
-    return HAVAC_OK;
-}
-}  // namespace
 
 extern "C" int havac_dev_write_sequence_records(havac_dev* d, const char* chars, uint64_t nchars, const uint64_t* record_ends,
                                                 uint32_t nrecords, uint64_t* record_starts_out) {
@@ -1480,46 +1383,26 @@ extern "C" int havac_dev_write_sequence_records(havac_dev* d, const char* chars,
     d->mask_bytes = 0;
     whole_copies(d);
     if (nbytes == 0) return HAVAC_OK;
-    const bool locked = nchars && hipHostRegister(const_cast<char*>(chars), nchars, hipHostRegisterDefault) == hipSuccess;
-    if (!locked) (void)hipGetLastError();
-    auto run = [&]() -> int {
-        for (DevicePart& p : d->parts) {
-            HIP_TRY(d->err, hipSetDevice(p.device));
-            if (p.seq_alloc < nbytes) {
-                if (p.d_seq) (void)hipFree(p.d_seq);
-                p.d_seq = nullptr; p.seq_alloc = 0;
-                HIP_TRY(d->err, hipMalloc(&p.d_seq, nbytes));
-                p.seq_alloc = nbytes;
-            }
-            if (p.mask_alloc < nbytes / 4) {
-                if (p.d_mask) (void)hipFree(p.d_mask);
-                p.d_mask = nullptr; p.mask_alloc = 0;
-                HIP_TRY(d->err, hipMalloc(&p.d_mask, nbytes / 4));
-                p.mask_alloc = nbytes / 4;
-            }
-            uint8_t* d_text = nullptr;
-            uint64_t *d_starts = nullptr, *d_begins = nullptr, *d_lens = nullptr;
-            auto release = [&]() { (void)hipFree(d_text); (void)hipFree(d_starts); (void)hipFree(d_begins); (void)hipFree(d_lens); };
-            int rc = to_device(d->err, reinterpret_cast<const uint8_t*>(chars), (size_t)nchars, &d_text, p.stream);
-            if (rc == HAVAC_OK) rc = to_device(d->err, starts.data(), starts.size(), &d_starts, p.stream);
-            if (rc == HAVAC_OK) rc = to_device(d->err, begins.data(), begins.size(), &d_begins, p.stream);
-            if (rc == HAVAC_OK) rc = to_device(d->err, lens.data(), lens.size(), &d_lens, p.stream);
-            if (rc != HAVAC_OK) { release(); return rc; }
-            const uint64_t words = ncolumns / 16;
-            hipLaunchKernelGGL(ssv_pack_records, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, p.stream,
-                               d_text, d_starts, d_begins, d_lens, nrecords, at, ncolumns,
-                               reinterpret_cast<uint32_t*>(p.d_seq), p.d_mask);
-            hipError_t e = hipStreamSynchronize(p.stream);
-            if (e == hipSuccess) e = hipGetLastError();
-            release();
-            if (e != hipSuccess) { d->err = hip_msg("packing the records", e); return HAVAC_E_RUNTIME; }
-        }
-        return HAVAC_OK;
-    };
-    const int rc = run();
-    if (locked) (void)hipHostUnregister(const_cast<char*>(chars));
-    if (rc == HAVAC_OK) d->mask_bytes = nbytes / 4;
-    return rc;
+    const auto locked = lock_source(d, chars, nchars, nchars != 0);
+    for (DevicePart& p : d->parts) {
+        HIP_TRY(d->err, hipSetDevice(p.device));
+        if (p.d_seq.capacity() < nbytes) HIP_TRY(d->err, p.d_seq.grow(nbytes));
+        if (p.d_mask.capacity() < nbytes / 4) HIP_TRY(d->err, p.d_mask.grow(nbytes / 4));
+        DeviceBuffer<uint8_t> d_text; DeviceBuffer<uint64_t> d_starts, d_begins, d_lens;
+        HIP_TRY(d->err, d_text.copy_from(reinterpret_cast<const uint8_t*>(chars), (size_t)nchars, p.stream));
+        HIP_TRY(d->err, d_starts.copy_from(starts.data(), starts.size(), p.stream));
+        HIP_TRY(d->err, d_begins.copy_from(begins.data(), begins.size(), p.stream));
+        HIP_TRY(d->err, d_lens.copy_from(lens.data(), lens.size(), p.stream));
+        const uint64_t words = ncolumns / 16;
+        hipLaunchKernelGGL(ssv_pack_records, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, p.stream,
+                           d_text.get(), d_starts.get(), d_begins.get(), d_lens.get(), nrecords, at, ncolumns,
+                           reinterpret_cast<uint32_t*>(p.d_seq.get()), p.d_mask.get());
+        hipError_t e = hipStreamSynchronize(p.stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) { d->err = hip_msg("packing the records", e); return HAVAC_E_RUNTIME; }
+    }
+    d->mask_bytes = nbytes / 4;
+    return HAVAC_OK;
 }
 
 extern "C" int havac_dev_append_reverse_strand(havac_dev* d, const uint64_t* starts, const uint64_t* residues, uint32_t nrecords,
@@ -1544,37 +1427,20 @@ extern "C" int havac_dev_append_reverse_strand(havac_dev* d, const uint64_t* sta
         }
     for (DevicePart& p : d->parts) {
         HIP_TRY(d->err, hipSetDevice(p.device));
-        if (p.seq_alloc < 2 * fbytes) {          // grow, keeping the forward half
-            uint8_t* bigger = nullptr;
-            HIP_TRY(d->err, hipMalloc(&bigger, 2 * fbytes));
-            hipError_t e = hipMemcpyAsync(bigger, p.d_seq, fbytes, hipMemcpyDeviceToDevice, p.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(p.stream);
-            if (e != hipSuccess) { (void)hipFree(bigger); d->err = hip_msg("growing the sequence buffer", e); return HAVAC_E_RUNTIME; }
-            (void)hipFree(p.d_seq);
-            p.d_seq = bigger; p.seq_alloc = 2 * fbytes;
-        }
-        uint64_t *d_starts = nullptr, *d_residues = nullptr;
-        int rc = to_device(d->err, starts, nrecords, &d_starts, p.stream);
-        if (rc == HAVAC_OK) rc = to_device(d->err, residues, nrecords, &d_residues, p.stream);
-        if (rc != HAVAC_OK) { (void)hipFree(d_starts); (void)hipFree(d_residues); return rc; }
+        if (p.d_seq.capacity() < 2 * fbytes) HIP_TRY(d->err, p.d_seq.grow_keeping(2 * fbytes, fbytes, p.stream));      // (the forward half)
+        DeviceBuffer<uint64_t> d_starts, d_residues;
+        HIP_TRY(d->err, d_starts.copy_from(starts, nrecords, p.stream));
+        HIP_TRY(d->err, d_residues.copy_from(residues, nrecords, p.stream));
         const uint64_t words = nf / 16;
         hipLaunchKernelGGL(ssv_reverse_strand, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, p.stream,
-                           reinterpret_cast<uint32_t*>(p.d_seq), nf, d_starts, d_residues, nrecords);
+                           reinterpret_cast<uint32_t*>(p.d_seq.get()), nf, d_starts.get(), d_residues.get(), nrecords);
         hipError_t e = hipSuccess;
         if (d->mask_bytes) {                        // the second half has the separators of the first
-            if (p.mask_alloc < 2 * d->mask_bytes) {
-                uint8_t* bigger = nullptr;
-                e = hipMalloc(&bigger, 2 * d->mask_bytes);
-                if (e == hipSuccess) e = hipMemcpyAsync(bigger, p.d_mask, d->mask_bytes, hipMemcpyDeviceToDevice, p.stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(p.stream);
-                if (e == hipSuccess) { (void)hipFree(p.d_mask); p.d_mask = bigger; p.mask_alloc = 2 * d->mask_bytes; }
-                else if (bigger) (void)hipFree(bigger);
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(p.d_mask + d->mask_bytes, p.d_mask, d->mask_bytes, hipMemcpyDeviceToDevice, p.stream);
+            if (p.d_mask.capacity() < 2 * d->mask_bytes) e = p.d_mask.grow_keeping(2 * d->mask_bytes, d->mask_bytes, p.stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(p.d_mask.get() + d->mask_bytes, p.d_mask.get(), d->mask_bytes, hipMemcpyDeviceToDevice, p.stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(p.stream);
         if (e == hipSuccess) e = hipGetLastError();
-        (void)hipFree(d_starts); (void)hipFree(d_residues);
         if (e != hipSuccess) { d->err = hip_msg("appending the second strand", e); return HAVAC_E_RUNTIME; }
     }
     d->seq_bytes = 2 * fbytes;
@@ -1594,8 +1460,8 @@ extern "C" int havac_dev_write_separator_mask(havac_dev* d, const uint8_t* pair_
     }
     d->mask_bytes = nbytes;
     // (the same columns per GPU as the sequence it belongs to)
-    if (d->parts[0].win_columns == 0) return upload(d, &DevicePart::d_mask, &DevicePart::mask_alloc, pair_bitmap, nbytes);
-    return upload_columns(d, &DevicePart::d_mask, &DevicePart::mask_alloc, pair_bitmap, d->seq_bytes * 4, 16);
+    if (d->parts[0].win_columns == 0) return upload(d, &DevicePart::d_mask, pair_bitmap, nbytes);
+    return upload_columns(d, &DevicePart::d_mask, pair_bitmap, d->seq_bytes * 4, 16);
 }
 
 extern "C" int havac_dev_write_phmm(havac_dev* d, const int8_t* scores, uint64_t nbytes) {
@@ -1614,7 +1480,7 @@ extern "C" int havac_dev_write_phmm(havac_dev* d, const int8_t* scores, uint64_t
     if (int rc = wait_inputs_read(d, false)) return rc;
     d->phmm_bytes = nbytes;
     if (nbytes == 0) return HAVAC_OK;
-    return upload(d, &DevicePart::d_phmm, &DevicePart::phmm_alloc, scores, nbytes);
+    return upload(d, &DevicePart::d_phmm, scores, nbytes);
 }
 
 // ---- runs ----------------------------------------------------------------------------------------------------------------
@@ -1645,12 +1511,12 @@ extern "C" int havac_dev_run_async(havac_dev* d) {
         DevicePart& p = d->parts[i];
         HIP_TRY(d->err, hipSetDevice(p.device));
         havac_ssv_ctx* const ctx = havac_pipe_context(p.pipe, -2);          // the slot this run will take
-        havac_ssv_set_separator_mask(ctx, d->mask_bytes ? p.d_mask : nullptr);
+        havac_ssv_set_separator_mask(ctx, d->mask_bytes ? p.d_mask.get() : nullptr);
         havac_ssv_set_sequence_window(ctx, p.win_first, p.win_columns);
         // (nothing to wait for: every write_* entry point returns with its upload complete; and the abort words are zero -- the run
         // that was aborted last put its own back, see dev_finish -- so a run costs no fill and no event in front of its first kernel)
-        int rc = havac_pipe_submit(p.pipe, p.d_seq, d->seq_bytes * 4, p.d_phmm, (uint32_t)(d->phmm_bytes / 4), i, nparts,
-                                   p.d_abort + run.abort_word, HAVAC_NO_STREAM);
+        int rc = havac_pipe_submit(p.pipe, p.d_seq.get(), d->seq_bytes * 4, p.d_phmm.get(), (uint32_t)(d->phmm_bytes / 4), i, nparts,
+                                   p.d_abort.get() + run.abort_word, HAVAC_NO_STREAM);
         if (rc) {
             d->err = havac_pipe_last_error(p.pipe);
             // take back what the earlier GPUs were given: they are the newest pass of their pipes; every older open run is finished
@@ -1704,7 +1570,7 @@ static int dev_finish(havac_dev* d, Run& r) {
             if (rc == HAVAC_E_HIT_OVERFLOW) r.overflowed = true;
         }
         if (r.abort_requested) {      // the word this run was stopped through is put back for the runs to come
-            (void)hipMemsetAsync(p.d_abort + r.abort_word, 0, sizeof(uint32_t), p.abort_stream);
+            (void)hipMemsetAsync(p.d_abort.get() + r.abort_word, 0, sizeof(uint32_t), p.abort_stream);
             (void)hipStreamSynchronize(p.abort_stream);
         }
     }
@@ -1764,7 +1630,7 @@ extern "C" int havac_dev_abort(havac_dev* d) {
         r.abort_requested = true;
         for (DevicePart& p : d->parts) {
             hipError_t e = hipSetDevice(p.device);
-            if (e == hipSuccess) e = hipMemcpyAsync(p.d_abort + r.abort_word, &one, sizeof one, hipMemcpyHostToDevice, p.abort_stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(p.d_abort.get() + r.abort_word, &one, sizeof one, hipMemcpyHostToDevice, p.abort_stream);
             if (e == hipSuccess) e = hipStreamSynchronize(p.abort_stream);
             if (e != hipSuccess) { d->err = hip_msg("abort", e); cur.finished = true; cur.failed = true; return HAVAC_STATE_ERROR; }
         }

@@ -35,6 +35,11 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include "hip_memory.h"
+
+using havac::DeviceBuffer;
+using havac::PinnedBuffer;
+
 namespace {
 
 struct Rccl {
@@ -97,8 +102,8 @@ struct havac_gather {
     int device = 0;
     hipStream_t stream = nullptr;          // every operation of this communicator runs here, in the order it was asked for
     hipEvent_t before = nullptr, after = nullptr;
-    int64_t* d_counts = nullptr;           // world + 1 words: [0..world) the gathered counts, [world] this rank's own
-    int64_t* h_counts = nullptr;           // pinned, same layout
+    DeviceBuffer<int64_t> d_counts;        // world + 1 words: [0..world) the gathered counts, [world] this rank's own
+    PinnedBuffer<int64_t> h_counts;        // same layout
     std::vector<int64_t> counts;           // of the last havac_gather_counts
     bool counted = false, broken = false;
     bool records_pending = false;          // havac_gather_records enqueued something `after` has not been seen to pass
@@ -106,14 +111,6 @@ struct havac_gather {
     std::string err;
 };
 
-#define GATHER_HIP(g, expr)                                                                     \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) {                                                                 \
-            (g)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
-            return _e == hipErrorOutOfMemory ? HAVAC_E_NOMEM : HAVAC_E_RUNTIME;                 \
-        }                                                                                       \
-    } while (0)
 #define GATHER_NCCL(g, expr)                                                                    \
     do {                                                                                        \
         ncclResult_t _r = (expr);                                                               \
@@ -169,7 +166,7 @@ extern "C" int havac_gather_wait(havac_gather* g) {
     if (!g) return HAVAC_E_ARGUMENT;
     if (!g->records_pending) return HAVAC_OK;
     if (g->broken) { g->err = "the communicator is broken (an earlier operation failed): destroy it"; return HAVAC_E_LOGIC; }
-    GATHER_HIP(g, hipSetDevice(g->device));
+    HIP_TRY(g->err, hipSetDevice(g->device));
     const int rc = wait_with_deadline(g, g->after, "the gather of the records (ncclSend / ncclRecv)");
     if (rc == HAVAC_OK) g->records_pending = false;
     return rc;
@@ -207,9 +204,7 @@ extern "C" void havac_gather_destroy(havac_gather* g) {
     if (g->before) (void)hipEventDestroy(g->before);
     if (g->after) (void)hipEventDestroy(g->after);
     if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->d_counts) (void)hipFree(g->d_counts);
-    if (g->h_counts) (void)hipHostFree(g->h_counts);
-    delete g;
+    delete g;          // (the count buffers, with this device current)
 }
 
 extern "C" int havac_gather_create(uint32_t rank, uint32_t world, const uint8_t id[HAVAC_GATHER_ID_BYTES], havac_gather** out) {
@@ -224,20 +219,20 @@ extern "C" int havac_gather_create(uint32_t rank, uint32_t world, const uint8_t 
     g->lib = lib; g->rank = rank; g->world = world; g->counts.assign(world, 0);
     auto fail = [&](int code) { std::fprintf(stderr, "havac_gather_create: %s\n", g->err.c_str()); havac_gather_destroy(g); return code; };
     auto body = [&]() -> int {
-        GATHER_HIP(g, hipGetDevice(&g->device));
+        HIP_TRY(g->err, hipGetDevice(&g->device));
         int least = 0, greatest = 0;
-        GATHER_HIP(g, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(g->err, hipDeviceGetStreamPriorityRange(&least, &greatest));
         // HIGH priority, as the pipe's kernel streams (round 5; rounds 3-4: low, "the gather must not take the next kernel's compute
         // units").  The gather of pass k runs beside the SSV kernels of passes k + 1 and k + 2, which always have workgroups waiting
         // for a wave slot: a low-priority launch beside them waits 30 - 330 us on average for its first slot (measured with this
         // round's ordering kernels), and here the HOST waits for the count exchange -- eight ranks' worth of
         // such delays, the slowest one counts -- before it can submit the pass after next.  What the collective's few workgroups
         // take from an SSV kernel for the 0.2 ms of an 8 MB transfer is below a per cent; a pipeline that runs dry is not.
-        GATHER_HIP(g, hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, greatest));
-        GATHER_HIP(g, hipEventCreateWithFlags(&g->before, hipEventDisableTiming));
-        GATHER_HIP(g, hipEventCreateWithFlags(&g->after, hipEventDisableTiming));
-        GATHER_HIP(g, hipMalloc(&g->d_counts, ((size_t)world + 1) * sizeof(int64_t)));
-        GATHER_HIP(g, hipHostMalloc(&g->h_counts, ((size_t)world + 1) * sizeof(int64_t), hipHostMallocDefault));
+        HIP_TRY(g->err, hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, greatest));
+        HIP_TRY(g->err, hipEventCreateWithFlags(&g->before, hipEventDisableTiming));
+        HIP_TRY(g->err, hipEventCreateWithFlags(&g->after, hipEventDisableTiming));
+        HIP_TRY(g->err, g->d_counts.grow((size_t)world + 1));
+        HIP_TRY(g->err, g->h_counts.allocate((size_t)world + 1));
         ncclUniqueId u;
         std::memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
         GATHER_NCCL(g, lib->CommInitRank(&g->comm, (int)world, u, (int)rank));      // collective: returns when every rank has called it
@@ -263,19 +258,21 @@ extern "C" int havac_gather_counts(havac_gather* g, int64_t my_count, int64_t* c
     if (!g || !counts_out) return HAVAC_E_ARGUMENT;
     if (g->broken) { g->err = "the communicator is broken (an earlier operation failed): destroy it"; return HAVAC_E_LOGIC; }
     const hipStream_t caller = (hipStream_t)hip_stream;
-    GATHER_HIP(g, hipSetDevice(g->device));
+    HIP_TRY(g->err, hipSetDevice(g->device));
     g->counted = false;
     // behind whatever the caller has queued (its pass's ordering), on the communicator's own stream
-    GATHER_HIP(g, hipEventRecord(g->before, caller));
-    GATHER_HIP(g, hipStreamWaitEvent(g->stream, g->before, 0));
-    g->h_counts[g->world] = my_count;
-    GATHER_HIP(g, hipMemcpyAsync(g->d_counts + g->world, g->h_counts + g->world, sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
-    GATHER_NCCL(g, g->lib->AllGather(g->d_counts + g->world, g->d_counts, 1, ncclInt64, g->comm, g->stream));
-    GATHER_HIP(g, hipMemcpyAsync(g->h_counts, g->d_counts, (size_t)g->world * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    GATHER_HIP(g, hipEventRecord(g->after, g->stream));
+    HIP_TRY(g->err, hipEventRecord(g->before, caller));
+    HIP_TRY(g->err, hipStreamWaitEvent(g->stream, g->before, 0));
+    int64_t* const h_counts = g->h_counts.get();
+    int64_t* const d_counts = g->d_counts.get();
+    h_counts[g->world] = my_count;
+    HIP_TRY(g->err, hipMemcpyAsync(d_counts + g->world, h_counts + g->world, sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+    GATHER_NCCL(g, g->lib->AllGather(d_counts + g->world, d_counts, 1, ncclInt64, g->comm, g->stream));
+    HIP_TRY(g->err, hipMemcpyAsync(h_counts, d_counts, (size_t)g->world * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g->err, hipEventRecord(g->after, g->stream));
     if (const int rc = wait_with_deadline(g, g->after, "the exchange of the counts (ncclAllGather)")) return rc;
     g->records_pending = false;            // (the stream is in order: whatever was queued before the counts has passed too)
-    for (uint32_t r = 0; r < g->world; r++) counts_out[r] = g->counts[r] = g->h_counts[r];
+    for (uint32_t r = 0; r < g->world; r++) counts_out[r] = g->counts[r] = h_counts[r];
     g->counted = true;
     return HAVAC_OK;
 }
@@ -301,9 +298,9 @@ extern "C" int havac_gather_records(havac_gather* g, const uint64_t* d_records, 
         return HAVAC_E_LENGTH;
     }
     const hipStream_t caller = (hipStream_t)hip_stream;
-    GATHER_HIP(g, hipSetDevice(g->device));
-    GATHER_HIP(g, hipEventRecord(g->before, caller));
-    GATHER_HIP(g, hipStreamWaitEvent(g->stream, g->before, 0));
+    HIP_TRY(g->err, hipSetDevice(g->device));
+    HIP_TRY(g->err, hipEventRecord(g->before, caller));
+    HIP_TRY(g->err, hipStreamWaitEvent(g->stream, g->before, 0));
     if (g->world > 1) {
         GATHER_NCCL(g, g->lib->GroupStart());
         // (a failure between GroupStart and GroupEnd must not leave the thread's group open: the group is closed first, the
@@ -329,9 +326,9 @@ extern "C" int havac_gather_records(havac_gather* g, const uint64_t* d_records, 
         }
     }
     if (g->rank == 0 && mine && d_out != d_records)
-        GATHER_HIP(g, hipMemcpyAsync(d_out, d_records, (size_t)mine * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream));
-    GATHER_HIP(g, hipEventRecord(g->after, g->stream));
-    GATHER_HIP(g, hipStreamWaitEvent(caller, g->after, 0));
+        HIP_TRY(g->err, hipMemcpyAsync(d_out, d_records, (size_t)mine * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream));
+    HIP_TRY(g->err, hipEventRecord(g->after, g->stream));
+    HIP_TRY(g->err, hipStreamWaitEvent(caller, g->after, 0));
     g->records_pending = true;
     return HAVAC_OK;
 }

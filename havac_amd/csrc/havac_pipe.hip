@@ -23,14 +23,17 @@
 
 #include <hip/hip_runtime.h>
 
-namespace {
+#include "hip_memory.h"
 
+using havac::DeviceBuffer;
+
+namespace {
 
 struct Slot {
     havac_ssv_ctx* ctx = nullptr;
-    uint64_t* d_hits = nullptr;
+    DeviceBuffer<uint64_t> d_hits;
     hipStream_t stream = nullptr;              // the stream the slot's pass in flight was submitted on
-    uint64_t* merged = nullptr; uint64_t merged_capacity = 0;      // rank 0 of a sharded run: the gather's receive buffer
+    DeviceBuffer<uint64_t> merged;             // rank 0 of a sharded run: the gather's receive buffer
     hipEvent_t gathered = nullptr;             // behind the slot's last gather: its hit buffer may be written again
     hipEvent_t g0 = nullptr, g1 = nullptr;     // timing of the slot's last gather
     bool timed = false;
@@ -53,39 +56,25 @@ struct havac_pipe {
     havac_gather* gather = nullptr; uint32_t rank = 0, world = 1;
     hipEvent_t inputs = nullptr;               // the caller's stream at submit time
     std::vector<float> gather_ms;
-    const uint64_t* last_records = nullptr;    // what the last collect returned (kept by release)
+    const uint64_t* last_records = nullptr;    // what the last collect returned: a slot's d_hits or merged, or `kept`
+    DeviceBuffer<uint64_t> kept;               // release(): the buffer of last_records, valid until the pipe is destroyed
     bool released = false;
     std::string err;
 };
-
-#define PIPE_HIP(p, expr)                                                                       \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) {                                                                 \
-            (p)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
-            return _e == hipErrorOutOfMemory ? HAVAC_E_NOMEM : HAVAC_E_RUNTIME;                 \
-        }                                                                                       \
-    } while (0)
-
-static void free_slot(Slot& s, const uint64_t* keep) {
-    if (s.ctx) { havac_ssv_ctx_destroy(s.ctx); s.ctx = nullptr; }
-    if (s.d_hits && s.d_hits != keep) { (void)hipFree(s.d_hits); s.d_hits = nullptr; }
-    if (s.merged && s.merged != keep) { (void)hipFree(s.merged); s.merged = nullptr; s.merged_capacity = 0; }
-}
 
 extern "C" void havac_pipe_destroy(havac_pipe* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     for (int k = 0; k < 4; k++) if (p->kstream[k]) (void)hipStreamSynchronize(p->kstream[k]);
     for (Slot& s : p->slots) {
-        free_slot(s, nullptr);
+        if (s.ctx) havac_ssv_ctx_destroy(s.ctx);
         if (s.gathered) (void)hipEventDestroy(s.gathered);
         if (s.g0) (void)hipEventDestroy(s.g0);
         if (s.g1) (void)hipEventDestroy(s.g1);
     }
     if (p->inputs) (void)hipEventDestroy(p->inputs);
     for (int k = 0; k < 4; k++) if (p->kstream[k]) (void)hipStreamDestroy(p->kstream[k]);
-    delete p;
+    delete p;          // (the hit and receive buffers, with this device current)
 }
 
 extern "C" int havac_pipe_create(uint32_t depth, uint64_t hit_capacity, int kernel_streams, havac_pipe** out) {
@@ -102,23 +91,23 @@ extern "C" int havac_pipe_create(uint32_t depth, uint64_t hit_capacity, int kern
     // something a rule can be built on; two streams have measured the same on every box of rounds 4 and 5.)
     p->kernel_streams = kernel_streams < 0 ? std::min<int>(2, (int)depth) : std::min<int>(kernel_streams, (int)depth);
     auto body = [&]() -> int {
-        PIPE_HIP(p, hipGetDevice(&p->device));
+        HIP_TRY(p->err, hipGetDevice(&p->device));
         int least = 0, greatest = 0;
-        PIPE_HIP(p, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(p->err, hipDeviceGetStreamPriorityRange(&least, &greatest));
         // High priority.  Two streams where passes are in flight: a pass -- its preparation, its SSV kernel, the ordering of its
         // records -- is one stream's business, consecutive passes alternate, so a kernel starts while its predecessor drains (the
         // last, half-empty round of a launch's tiles and the ~16 us between two dependent launches are filled by its neighbour's
         // first workgroups: C2 1.878 -> 1.78 ms per step, less than one kernel takes alone) and runs beside its predecessor's ordering
-        for (int k = 0; k < p->kernel_streams; k++) PIPE_HIP(p, hipStreamCreateWithPriority(&p->kstream[k], hipStreamNonBlocking, greatest));
+        for (int k = 0; k < p->kernel_streams; k++) HIP_TRY(p->err, hipStreamCreateWithPriority(&p->kstream[k], hipStreamNonBlocking, greatest));
         (void)least;
-        PIPE_HIP(p, hipEventCreateWithFlags(&p->inputs, hipEventDisableTiming));
+        HIP_TRY(p->err, hipEventCreateWithFlags(&p->inputs, hipEventDisableTiming));
         p->slots.resize(depth);
         for (Slot& s : p->slots) {
             if (havac_ssv_ctx_create(&s.ctx) != HAVAC_OK) { p->err = "could not create an SSV context"; return HAVAC_E_RUNTIME; }
-            if (hit_capacity) PIPE_HIP(p, hipMalloc(&s.d_hits, hit_capacity * sizeof(uint64_t)));
-            PIPE_HIP(p, hipEventCreateWithFlags(&s.gathered, hipEventDisableTiming));
-            PIPE_HIP(p, hipEventCreate(&s.g0));
-            PIPE_HIP(p, hipEventCreate(&s.g1));
+            if (hit_capacity) HIP_TRY(p->err, s.d_hits.grow(hit_capacity));
+            HIP_TRY(p->err, hipEventCreateWithFlags(&s.gathered, hipEventDisableTiming));
+            HIP_TRY(p->err, hipEventCreate(&s.g0));
+            HIP_TRY(p->err, hipEventCreate(&s.g1));
         }
         return HAVAC_OK;
     };
@@ -154,7 +143,7 @@ extern "C" int havac_pipe_submit(havac_pipe* p, const uint8_t* d_sequence, uint6
     if (!p) return HAVAC_E_ARGUMENT;
     if (p->released) { p->err = "the pipe was released"; return HAVAC_E_LOGIC; }
     if (p->in_flight.size() == p->depth) { p->err = "every slot is in flight: collect first"; return HAVAC_E_LOGIC; }
-    PIPE_HIP(p, hipSetDevice(p->device));
+    HIP_TRY(p->err, hipSetDevice(p->device));
     Slot& s = p->slots[p->next];
     hipStream_t stream = p->kstream[0];
     if (p->kstream[1]) {
@@ -168,11 +157,11 @@ extern "C" int havac_pipe_submit(havac_pipe* p, const uint8_t* d_sequence, uint6
     // the caller's inputs (HAVAC_NO_STREAM: they are in place, nothing to wait for -- an event on the legacy null stream alone
     // costs a strictly serial 0.2 ms pass 5 %); and, in a sharded run, the slot's last gather, which reads the hit buffer this pass writes
     if (caller_stream != HAVAC_NO_STREAM) {
-        PIPE_HIP(p, hipEventRecord(p->inputs, (hipStream_t)caller_stream));
-        PIPE_HIP(p, hipStreamWaitEvent(stream, p->inputs, 0));
+        HIP_TRY(p->err, hipEventRecord(p->inputs, (hipStream_t)caller_stream));
+        HIP_TRY(p->err, hipStreamWaitEvent(stream, p->inputs, 0));
     }
-    if (p->gather) PIPE_HIP(p, hipStreamWaitEvent(stream, s.gathered, 0));
-    const int rc = havac_ssv_enqueue(s.ctx, d_sequence, nsymbols, d_phmm, nrows, shard_index, shard_count, s.d_hits, p->hit_capacity, d_abort_flag, stream);
+    if (p->gather) HIP_TRY(p->err, hipStreamWaitEvent(stream, s.gathered, 0));
+    const int rc = havac_ssv_enqueue(s.ctx, d_sequence, nsymbols, d_phmm, nrows, shard_index, shard_count, s.d_hits.get(), p->hit_capacity, d_abort_flag, stream);
     if (rc) { p->err = havac_ssv_ctx_last_error(s.ctx); return rc; }
     p->in_flight.push_back(p->next);
     p->next = (p->next + 1) % p->depth;
@@ -204,7 +193,7 @@ static void harvest(havac_pipe* p, Slot& s) {
 extern "C" int havac_pipe_collect(havac_pipe* p, uint64_t* found_out, const uint64_t** d_records_out, uint64_t* nrecords_out, void* caller_stream) {
     if (!p) return HAVAC_E_ARGUMENT;
     if (p->in_flight.empty()) { p->err = "nothing in flight"; return HAVAC_E_LOGIC; }
-    PIPE_HIP(p, hipSetDevice(p->device));
+    HIP_TRY(p->err, hipSetDevice(p->device));
     const uint32_t slot = p->in_flight.front();
     p->in_flight.pop_front();
     p->last = slot;
@@ -217,8 +206,8 @@ extern "C" int havac_pipe_collect(havac_pipe* p, uint64_t* found_out, const uint
     if (nrecords_out) *nrecords_out = 0;
     if (!p->gather) {
         if (pass_rc) return pass_rc;
-        p->last_records = s.d_hits;
-        if (d_records_out) *d_records_out = s.d_hits;
+        p->last_records = s.d_hits.get();
+        if (d_records_out) *d_records_out = s.d_hits.get();
         if (nrecords_out) *nrecords_out = found;
         return HAVAC_OK;
     }
@@ -227,7 +216,7 @@ extern "C" int havac_pipe_collect(havac_pipe* p, uint64_t* found_out, const uint
     if (caller_stream == HAVAC_NO_STREAM) caller_stream = nullptr;
     const hipStream_t stream = s.stream ? s.stream : (hipStream_t)caller_stream;      // (idle: the pass has been waited for; the next pass of this slot queues behind)
     harvest(p, s);
-    PIPE_HIP(p, hipEventRecord(s.g0, stream));
+    HIP_TRY(p->err, hipEventRecord(s.g0, stream));
     std::vector<int64_t> counts(p->world, 0);
     int rc = havac_gather_counts(p->gather, pass_rc ? -1 : (int64_t)found, counts.data(), stream);
     if (rc) { p->err = havac_gather_last_error(p->gather); return rc; }
@@ -242,22 +231,20 @@ extern "C" int havac_pipe_collect(havac_pipe* p, uint64_t* found_out, const uint
         p->err = "the pass failed on rank(s) " + failed + "; no records were gathered";
         return HAVAC_E_RUNTIME;
     }
-    if (p->rank == 0 && s.merged_capacity < total) {
-        PIPE_HIP(p, hipStreamSynchronize(stream));              // (the buffer's last gather)
-        if (s.merged) { if (s.merged == p->last_records) p->last_records = nullptr; (void)hipFree(s.merged); }      // (its records were valid until this slot was submitted again)
-        s.merged = nullptr; s.merged_capacity = 0;
-        PIPE_HIP(p, hipMalloc(&s.merged, std::max<uint64_t>(total, 1) * sizeof(uint64_t)));
-        s.merged_capacity = std::max<uint64_t>(total, 1);
+    if (p->rank == 0 && s.merged.capacity() < total) {
+        HIP_TRY(p->err, hipStreamSynchronize(stream));              // (the buffer's last gather)
+        if (s.merged.get() == p->last_records) p->last_records = nullptr;      // (its records were valid until this slot was submitted again)
+        HIP_TRY(p->err, s.merged.grow(std::max<uint64_t>(total, 1)));
     }
-    rc = havac_gather_records(p->gather, s.d_hits, p->rank == 0 ? s.merged : nullptr, s.merged_capacity, stream);
+    rc = havac_gather_records(p->gather, s.d_hits.get(), p->rank == 0 ? s.merged.get() : nullptr, s.merged.capacity(), stream);
     if (rc) { p->err = havac_gather_last_error(p->gather); return rc; }
-    PIPE_HIP(p, hipEventRecord(s.g1, stream));
+    HIP_TRY(p->err, hipEventRecord(s.g1, stream));
     s.timed = true;
-    PIPE_HIP(p, hipEventRecord(s.gathered, stream));
-    if (stream != (hipStream_t)caller_stream) PIPE_HIP(p, hipStreamWaitEvent((hipStream_t)caller_stream, s.gathered, 0));      // the records are the caller's
+    HIP_TRY(p->err, hipEventRecord(s.gathered, stream));
+    if (stream != (hipStream_t)caller_stream) HIP_TRY(p->err, hipStreamWaitEvent((hipStream_t)caller_stream, s.gathered, 0));      // the records are the caller's
     if (p->rank == 0) {
-        p->last_records = s.merged;
-        if (d_records_out) *d_records_out = s.merged;
+        p->last_records = s.merged.get();
+        if (d_records_out) *d_records_out = s.merged.get();
         if (nrecords_out) *nrecords_out = total;
     }
     return HAVAC_OK;
@@ -328,11 +315,15 @@ extern "C" int havac_pipe_last_ms(havac_pipe* p, float* ssv_kernel_ms, float* to
 extern "C" int havac_pipe_release(havac_pipe* p) {
     if (!p) return HAVAC_E_ARGUMENT;
     if (!p->in_flight.empty()) { p->err = "passes are in flight: collect them first"; return HAVAC_E_LOGIC; }
-    PIPE_HIP(p, hipSetDevice(p->device));
-    for (int k = 0; k < 4; k++) if (p->kstream[k]) PIPE_HIP(p, hipStreamSynchronize(p->kstream[k]));
+    HIP_TRY(p->err, hipSetDevice(p->device));
+    for (int k = 0; k < 4; k++) if (p->kstream[k]) HIP_TRY(p->err, hipStreamSynchronize(p->kstream[k]));
     for (Slot& s : p->slots) {
         harvest(p, s);
-        free_slot(s, p->last_records);
+        if (s.ctx) { havac_ssv_ctx_destroy(s.ctx); s.ctx = nullptr; }
+        for (DeviceBuffer<uint64_t>* b : {&s.d_hits, &s.merged}) {
+            if (b->get() && b->get() == p->last_records) p->kept = std::move(*b);
+            b->reset();
+        }
     }
     p->released = true;
     return HAVAC_OK;
