@@ -47,6 +47,12 @@ SIGNATURES = {
     "havac_dev_read_hits": (C.c_int, [_vp, C.c_void_p, C.c_uint32]),
     "havac_dev_num_hits64": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "havac_dev_read_hits64": (C.c_int, [_vp, C.c_void_p, C.c_uint64]),
+    "havac_dev_compute_windows": (C.c_int, [_vp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "havac_dev_read_windows": (C.c_int, [_vp, C.c_uint64] + [C.c_void_p] * 8 + [C.POINTER(C.c_uint64)]),
+    "havac_dev_set_window_chunk": (C.c_int, [_vp, C.c_uint64]),
+    "havac_dev_window_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "havac_windows_join": (C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.POINTER(C.c_uint64)]),
     "havac_dev_last_run_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "havac_dev_last_error": (C.c_char_p, [_vp]),
     "havac_ssv_ctx_create": (C.c_int, [C.POINTER(C.c_void_p)]),

@@ -27,6 +27,7 @@
 #include "ssv_kernels.hip.h"
 #include "hit_order.hip.h"
 #include "hip_memory.h"
+#include "havac_windows.h"
 
 using namespace havac;
 
@@ -1001,6 +1002,7 @@ struct DevicePart {
     DeviceBuffer<char> d_chars[2];
     hipEvent_t chars_copied[2] = {nullptr, nullptr}, chars_packed[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr;
+    WindowScratch windows;              // havac_dev_compute_windows (havac_windows.h): not the pipe's slots, which the next run may use
 
     DevicePart() = default;
     DevicePart(DevicePart&&) = default;
@@ -1017,6 +1019,7 @@ struct Run {
     std::vector<const uint64_t*> part_records;     // each GPU's ordered list (device memory of its pipe's slot)
     float ssv_ms = 0.f, total_ms = 0.f;
     std::string err;
+    uint64_t serial = 0;               // which run of the handle (havac_dev_read_windows checks its windows are this run's)
 };
 
 constexpr uint32_t kMaxDepth = 4;
@@ -1030,6 +1033,11 @@ struct havac_dev {
     bool has_run = false;               // a run was started at some time (the reference's "run object was not initialized")
     uint64_t submitted = 0;
     std::string err;
+    // havac_dev_compute_windows: the windows of run `windows_run` (joined on the host; freed as havac_dev_read_windows copies them
+    // out), records per chunk (0: the default), bytes of windows the last compute copied from the GPUs
+    WindowBlocks windows;
+    bool have_windows = false;
+    uint64_t windows_run = 0, window_chunk = 0, windows_read_back = 0;
 };
 
 // the reference's fixed hit buffer: 14 * 256 MiB = 3.5 GiB = 469,762,048 records (host/HavacHwClient.hpp:94)
@@ -1506,6 +1514,7 @@ extern "C" int havac_dev_run_async(havac_dev* d) {
     }
     Run run;
     run.abort_word = (uint32_t)(d->submitted % kMaxDepth);
+    run.serial = d->submitted;
     run.part_found.assign(nparts, 0); run.part_records.assign(nparts, nullptr);
     for (uint32_t i = 0; i < nparts; i++) {
         DevicePart& p = d->parts[i];
@@ -1711,5 +1720,121 @@ extern "C" int havac_dev_last_run_ms(havac_dev* d, float* ssv_kernel_ms, float* 
     if (!d->has_run || d->runs.empty() || !d->runs.front().finished) { d->err = "no finished run"; return HAVAC_E_LOGIC; }
     if (ssv_kernel_ms) *ssv_kernel_ms = d->runs.front().ssv_ms;
     if (total_ms) *total_ms = d->runs.front().total_ms;
+    return HAVAC_OK;
+}
+
+// ---- windows of the oldest open run, made on the GPUs that hold its records (havac_windows.h) ----------------------------------
+extern "C" int havac_dev_set_window_chunk(havac_dev* d, uint64_t records) {
+    if (!d || records > kMaxWindowChunk) return HAVAC_E_ARGUMENT;
+    d->window_chunk = records;
+    return HAVAC_OK;
+}
+
+extern "C" int havac_dev_compute_windows(havac_dev* d, const uint64_t* record_ends, uint32_t nrecords, const uint32_t* model_lengths,
+                                         uint32_t nmodels, const uint64_t* record_starts, const uint64_t* record_columns,
+                                         const uint32_t* model_starts, uint64_t forward_columns, uint32_t flank, uint64_t* count) {
+    if (!d || !count || (nrecords && !record_ends) || (nmodels && !model_lengths)) return HAVAC_E_ARGUMENT;
+    const bool boundary = record_starts != nullptr;
+    if (boundary != (record_columns != nullptr) || (boundary && nmodels && !model_starts)) return HAVAC_E_ARGUMENT;
+    if (nmodels >= (1u << kWindowModelBits)) { d->err = "at most 2^24 - 1 models"; return HAVAC_E_ARGUMENT; }
+    d->windows = WindowBlocks();
+    d->have_windows = false;
+    d->windows_read_back = 0;
+    uint64_t found = 0;
+    if (int rc = havac_dev_num_hits64(d, &found)) return rc;          // (waits for the run; overflowed, aborted: no list)
+    const Run& cur = d->runs.front();
+    WindowTables t;
+    t.record_ends = record_ends; t.nrecords = nrecords; t.model_lengths = model_lengths; t.nmodels = nmodels;
+    t.record_starts = record_starts; t.record_columns = record_columns; t.model_starts = boundary ? model_starts : nullptr;
+    t.forward_columns = forward_columns; t.flank = flank;
+    const uint64_t chunk = d->window_chunk ? d->window_chunk : kDefaultWindowChunk;
+    // every GPU merges its own shard's records; a window may hold hits of several shards, so the GPUs' lists are joined again
+    // (on the host, as the chunks of one GPU are).  On each GPU's abort stream, as havac_dev_read_hits64 reads: the handle's own
+    // stream may already hold the next run's uploads.
+    std::vector<std::vector<WindowItem>> lists;
+    for (size_t i = 0; i < d->parts.size(); i++) {
+        DevicePart& p = d->parts[i];
+        if (cur.part_found[i] == 0) continue;
+        HIP_TRY(d->err, hipSetDevice(p.device));
+        if (int rc = upload_window_tables(d->err, p.windows, t, p.abort_stream)) return rc;
+        p.windows.read_back = 0;
+        const int rc = windows_of_records(d->err, p.windows, cur.part_records[i], cur.part_found[i], chunk, p.abort_stream, lists);
+        d->windows_read_back += p.windows.read_back;
+        if (rc) return rc;
+    }
+    try {
+        d->windows = join_window_lists(lists);
+    } catch (const std::bad_alloc&) {
+        d->err = "no host memory for the windows";
+        return HAVAC_E_NOMEM;
+    }
+    d->have_windows = true;
+    d->windows_run = cur.serial;
+    *count = d->windows.total;
+    return HAVAC_OK;
+}
+
+extern "C" int havac_dev_read_windows(havac_dev* d, uint64_t n, uint32_t* sequence_index, uint32_t* phmm_index, uint8_t* reverse_strand,
+                                      uint64_t* sequence_start, uint64_t* sequence_end, uint32_t* phmm_first, uint32_t* phmm_last,
+                                      uint32_t* hit_count, uint64_t* copied) {
+    if (!d || !copied) return HAVAC_E_ARGUMENT;
+    if (n && (!sequence_index || !phmm_index || !reverse_strand || !sequence_start || !sequence_end || !phmm_first || !phmm_last || !hit_count))
+        return HAVAC_E_ARGUMENT;
+    *copied = 0;
+    if (!d->have_windows || d->runs.empty() || d->runs.front().serial != d->windows_run) {
+        d->err = "no windows were computed for the oldest open run (havac_dev_compute_windows)";
+        return HAVAC_E_LOGIC;
+    }
+    *copied = d->windows.take(n, [&](uint64_t i, const WindowItem& w) {
+        sequence_index[i] = (uint32_t)(w.key >> kWindowRecordShift);
+        reverse_strand[i] = (uint8_t)((w.key >> kWindowStrandBit) & 1);
+        phmm_index[i] = (uint32_t)(w.key & ((1u << kWindowModelBits) - 1));
+        sequence_start[i] = w.start; sequence_end[i] = w.end;
+        phmm_first[i] = w.phmm_first; phmm_last[i] = w.phmm_last; hit_count[i] = w.hit_count;
+    });
+    return HAVAC_OK;
+}
+
+extern "C" int havac_dev_window_stats(havac_dev* d, uint64_t* scratch_bytes, uint64_t* read_back_bytes) {
+    if (!d) return HAVAC_E_ARGUMENT;
+    if (scratch_bytes) {
+        *scratch_bytes = 0;
+        for (const DevicePart& p : d->parts) *scratch_bytes = std::max(*scratch_bytes, p.windows.high_water);
+    }
+    if (read_back_bytes) *read_back_bytes = d->windows_read_back;
+    return HAVAC_OK;
+}
+
+extern "C" int havac_windows_join(uint64_t nwindows, const uint64_t* list_ends, uint32_t nlists, uint32_t* sequence_index,
+                                  uint32_t* phmm_index, uint8_t* reverse_strand, uint64_t* sequence_start, uint64_t* sequence_end,
+                                  uint32_t* phmm_first, uint32_t* phmm_last, uint32_t* hit_count, uint64_t* count) {
+    if (!count || (nlists && !list_ends) || (nwindows && (!sequence_index || !phmm_index || !reverse_strand || !sequence_start ||
+                                                         !sequence_end || !phmm_first || !phmm_last || !hit_count)))
+        return HAVAC_E_ARGUMENT;
+    try {
+        std::vector<std::vector<WindowItem>> lists;
+        uint64_t at = 0;
+        for (uint32_t l = 0; l < nlists; l++) {
+            if (list_ends[l] < at || list_ends[l] > nwindows) return HAVAC_E_ARGUMENT;
+            std::vector<WindowItem> list;
+            for (; at < list_ends[l]; at++) {
+                if (phmm_index[at] >= (1u << kWindowModelBits)) return HAVAC_E_ARGUMENT;
+                list.push_back(WindowItem{window_key(sequence_index[at], reverse_strand[at] != 0, phmm_index[at]), sequence_start[at],
+                                          sequence_end[at], phmm_first[at], phmm_last[at], hit_count[at], 0});
+            }
+            lists.push_back(std::move(list));
+        }
+        if (at != nwindows) return HAVAC_E_ARGUMENT;
+        WindowBlocks joined = join_window_lists(lists);
+        *count = joined.take(joined.total, [&](uint64_t i, const WindowItem& w) {
+            sequence_index[i] = (uint32_t)(w.key >> kWindowRecordShift);
+            reverse_strand[i] = (uint8_t)((w.key >> kWindowStrandBit) & 1);
+            phmm_index[i] = (uint32_t)(w.key & ((1u << kWindowModelBits) - 1));
+            sequence_start[i] = w.start; sequence_end[i] = w.end;
+            phmm_first[i] = w.phmm_first; phmm_last[i] = w.phmm_last; hit_count[i] = w.hit_count;
+        });
+    } catch (const std::bad_alloc&) {
+        return HAVAC_E_NOMEM;
+    }
     return HAVAC_OK;
 }

@@ -1,6 +1,6 @@
 // hip_memory.h -- who frees what: the owners of the HIP memory of libhavac_dev.so's host code, and its one error check.
 //
-// Internal to havac_dev.hip, havac_pipe.hip and havac_gather.hip (not ABI: include/ holds that).  No other code of theirs
+// Internal to havac_dev.hip, havac_pipe.hip, havac_gather.hip and havac_windows.hip (not ABI: include/ holds that).  No other code of theirs
 // calls hipMalloc / hipFree / hipHostMalloc / hipHostFree / hipHostRegister / hipHostUnregister: every array below is freed
 // once, on every path, by the object that owns it.
 #pragma once

@@ -309,7 +309,10 @@ vector<HavacHit> havacResolveHits(const vector<uint64_t> &rawHits, const FastaVe
 
 vector<HavacHit> Havac::getHitsFromFinishedRun() { return fetchHits(nullptr); }
 
-vector<HavacHit> Havac::fetchHits(RunInputs *inputsOut) {
+// The bookkeeping every fetch of the oldest open run shares: fetch(run, n) gets the inputs the run was started with and its record
+// count, and returns what the fetch returns.
+template <class F>
+auto Havac::fetchOldestRun(F &&fetch) {
     needDevice();
     // with several runs open, fetching a run's hits closes it -- also when it has no list (overflowed, aborted): the next call
     // speaks of the next run, and the run's inputs go with it
@@ -325,7 +328,14 @@ vector<HavacHit> Havac::fetchHits(RunInputs *inputsOut) {
         throw std::logic_error("the runs recorded by Havac are out of step with the device layer's open runs");
     uint64_t n = 0;                                        // 64-bit: several GPUs can hold more than 2^32 - 1 records
     check(havac_dev_num_hits64(dev_, &n));                 // (no open run: throws)
-    const RunInputs &run = runInputs_.front();             // (released before closeRun pops it)
+    return fetch(runInputs_.front(), n);                   // (released before closeRun pops it)
+}
+
+vector<HavacHit> Havac::fetchHits(RunInputs *inputsOut) {
+    return fetchOldestRun([&](const RunInputs &run, uint64_t n) { return resolveRun(run, n, inputsOut); });
+}
+
+vector<HavacHit> Havac::resolveRun(const RunInputs &run, uint64_t n, RunInputs *inputsOut) {
     if (inputsOut) *inputsOut = run;
     rawHits_.assign(n, 0);
     if (n) check(havac_dev_read_hits64(dev_, rawHits_.data(), n));
@@ -426,6 +436,22 @@ vector<HavacWindow> havacMergeHitsToWindows(const vector<HavacHit> &hits, const 
     return out;
 }
 
+vector<HavacWindow> havacWindowsOfRecords(const vector<uint64_t> &rawHits, const vector<uint64_t> &recordEnds,
+                                          const vector<uint32_t> &modelLengths, uint32_t flank) {
+    vector<uint32_t> prefixSums(1, 0u);
+    for (const uint32_t L : modelLengths) prefixSums.push_back(prefixSums.back() + L);
+    vector<HavacHit> hits = resolveAll(rawHits.size(), [&](size_t i, HavacHit *hit) {
+        return resolveOne(rawHits[i], i, recordEnds, prefixSums, hit);
+    });
+    vector<uint64_t> recordLengths;
+    uint64_t start = 0;
+    for (const uint64_t end : recordEnds) {
+        recordLengths.push_back(end > start ? end - start - 1 : 0);
+        start = end;
+    }
+    return havacMergeHitsToWindows(hits, modelLengths, recordLengths, flank);
+}
+
 vector<HavacWindow> Havac::getWindowsFromFinishedRun(uint32_t flank) {
     RunInputs run;
     vector<HavacHit> hits = fetchHits(&run);
@@ -436,6 +462,43 @@ vector<HavacWindow> Havac::getWindowsFromFinishedRun(uint32_t flank) {
         start = end;
     }
     return havacMergeHitsToWindows(hits, run.lengths, recordLengths, flank);
+}
+
+void Havac::setWindowChunk(uint64_t records) { needDevice(); check(havac_dev_set_window_chunk(dev_, records)); }
+
+uint64_t Havac::windowScratchBytes() {
+    needDevice();
+    uint64_t bytes = 0;
+    check(havac_dev_window_stats(dev_, &bytes, nullptr));
+    return bytes;
+}
+
+vector<HavacWindow> Havac::getDeviceWindowsFromFinishedRun(uint32_t flank) {
+    return fetchOldestRun([&](const RunInputs &run, uint64_t) {
+        // the device layer resolves against the same tables fetchHits uses; no record crosses PCIe, only the windows
+        const bool boundary = boundaryMode_;
+        uint64_t count = 0;
+        check(havac_dev_compute_windows(dev_, run.recordEnds.data(), (uint32_t)run.recordEnds.size(), run.lengths.data(),
+                                        (uint32_t)run.lengths.size(), boundary ? run.recordStarts.data() : nullptr,
+                                        boundary ? run.recordLengths.data() : nullptr, boundary ? run.starts.data() : nullptr,
+                                        run.bothStrands ? run.forwardColumns : 0, flank, &count));
+        // the device layer frees its copy block by block as it is read: read in slices into a small staging area and build the
+        // result as it comes (reserved, so that only the pages written are resident), never two whole copies at once
+        vector<HavacWindow> out;
+        out.reserve(count);
+        const uint64_t kSlice = 1u << 16;
+        vector<uint32_t> si(kSlice), pi(kSlice), pf(kSlice), pl(kSlice), hc(kSlice);
+        vector<uint8_t> rs(kSlice);
+        vector<uint64_t> start(kSlice), end(kSlice);
+        while (out.size() < count) {
+            uint64_t got = 0;
+            check(havac_dev_read_windows(dev_, kSlice, si.data(), pi.data(), rs.data(), start.data(), end.data(), pf.data(), pl.data(),
+                                         hc.data(), &got));
+            if (got == 0) throw std::logic_error("the device layer served fewer windows than it counted");
+            for (uint64_t i = 0; i < got; i++) out.push_back(HavacWindow{si[i], pi[i], rs[i] != 0, start[i], end[i], pf[i], pl[i], hc[i]});
+        }
+        return out;
+    });
 }
 
 HavacHit::HavacHit(const uint64_t sequencePosition, const uint32_t sequenceIndex, const uint32_t phmmPosition,

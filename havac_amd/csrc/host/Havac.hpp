@@ -105,6 +105,16 @@ public:
     void setBothStrands(bool on);
     // Hits of the finished run merged into windows (see HavacWindow); `flank` residues are added on both sides.
     vector<HavacWindow> getWindowsFromFinishedRun(uint32_t flank = 0);
+    // The same windows, element for element, made on the GPU(s) that hold the run's records: no record crosses to the host, only
+    // windows.  Host memory: the result (48 B per window) and, while the chunks' lists are joined, 40 B per chunk window -- about
+    // 90 B per window at most, against getWindowsFromFinishedRun's 80 B or more per RECORD; where hits cluster, windows are far
+    // fewer than records.  Fetches the run as getHitsFromFinishedRun does (waits, raises for an overflowed or aborted run, closes the
+    // run at depth > 1) but reads no record: rawHitsOfLastFetch() is empty afterwards.
+    vector<HavacWindow> getDeviceWindowsFromFinishedRun(uint32_t flank = 0);
+    // Records per chunk of that merge (0: the library's default; include/havac_dev.h: havac_dev_set_window_chunk), and the most
+    // device memory one GPU's merges have held, in bytes.
+    void setWindowChunk(uint64_t records);
+    uint64_t windowScratchBytes();
     // Packing on the GPU, on by default: loadSequence sends the text (and, in the plain
     // mode, the symbols it drew for the non-a/c/g/t columns); the boundary-mode layout and the second strand are made
     // on the GPU as well.  The device buffers are byte for byte what the host packer (SequencePreprocessor) would have
@@ -159,6 +169,9 @@ private:
     std::deque<RunInputs> runInputs_;                      // one per open run, oldest first
     uint32_t pipelineDepth_ = 1;
     vector<HavacHit> fetchHits(RunInputs *inputsOut);
+    vector<HavacHit> resolveRun(const RunInputs &run, uint64_t n, RunInputs *inputsOut);
+    template <class F>
+    auto fetchOldestRun(F &&fetch);
 };
 
 // The resolver of host/Havac.cpp:145-187 as a free function (testable without a device):
@@ -175,4 +188,8 @@ vector<HavacHit> havacResolveHits(const vector<uint64_t> &rawHits, const FastaVe
 // Output order: record, strand (forward first), model, start.
 vector<HavacWindow> havacMergeHitsToWindows(const vector<HavacHit> &hits, const vector<uint32_t> &modelLengths,
                                             const vector<uint64_t> &recordLengths, uint32_t flank = 0);
+// What getWindowsFromFinishedRun computes after its read-back, for the plain layout and one strand, on explicit tables: raw
+// records -> resolved hits (on the host's threads) -> havacMergeHitsToWindows.  recordEnds as FastaVector's sequenceEndPosition.
+vector<HavacWindow> havacWindowsOfRecords(const vector<uint64_t> &rawHits, const vector<uint64_t> &recordEnds,
+                                          const vector<uint32_t> &modelLengths, uint32_t flank = 0);
 #endif

@@ -21,6 +21,9 @@ struct havac_host {
     vector<HavacWindow> windows;                 // the same for havac_host_get_windows (with the flank they were made with)
     bool haveWindows = false;
     uint32_t windowsFlank = 0;
+    vector<HavacWindow> deviceWindows;           // the same for havac_host_get_device_windows
+    bool haveDeviceWindows = false;
+    uint32_t deviceWindowsFlank = 0;
     uint32_t depth = 1;
 };
 
@@ -96,21 +99,21 @@ const char *havac_host_last_error(havac_host *h) { return h ? h->err.c_str() : "
 
 int havac_host_load_sequence(havac_host *h, const char *p) { return guarded(h, [&] { h->obj->loadSequence(p); }); }
 int havac_host_load_phmm(havac_host *h, const char *p) { return guarded(h, [&] { h->obj->loadPhmm(p); }); }
-int havac_host_run(havac_host *h) { h->haveHits = h->haveWindows = false; return guarded(h, [&] { h->obj->runHardwareClient(); }); }
+int havac_host_run(havac_host *h) { h->haveHits = h->haveWindows = h->haveDeviceWindows = false; return guarded(h, [&] { h->obj->runHardwareClient(); }); }
 int havac_host_run_async(havac_host *h) {
-    h->haveHits = h->haveWindows = false;
+    h->haveHits = h->haveWindows = h->haveDeviceWindows = false;
     return guarded(h, [&] { h->obj->runHardwareClientAsync(); });
 }
 int havac_host_wait(havac_host *h) { return guarded(h, [&] { h->obj->waitHardwareClientAsync(); }); }
 int havac_host_abort(havac_host *h) { return guarded(h, [&] { h->obj->abortHardwareClient(); }); }
 int havac_host_set_hit_capacity(havac_host *h, uint64_t n) {
     const int rc = guarded(h, [&] { h->obj->setHitCapacity(n); });
-    if (rc == HAVAC_OK) h->haveHits = h->haveWindows = false;     // (new hit buffers: every run is closed)
+    if (rc == HAVAC_OK) h->haveHits = h->haveWindows = h->haveDeviceWindows = false;     // (new hit buffers: every run is closed)
     return rc;
 }
 int havac_host_set_pipeline_depth(havac_host *h, uint32_t depth) {
     const int rc = guarded(h, [&] { h->obj->setPipelineDepth(depth); });
-    if (rc == HAVAC_OK) { h->depth = depth; h->haveHits = h->haveWindows = false; }
+    if (rc == HAVAC_OK) { h->depth = depth; h->haveHits = h->haveWindows = h->haveDeviceWindows = false; }
     return rc;
 }
 // With several runs open havac_host_get_hits (havac_host_get_windows) fetches (and closes) the oldest run once and then serves the
@@ -118,7 +121,7 @@ int havac_host_set_pipeline_depth(havac_host *h, uint32_t depth) {
 // havac_host_get_hits (havac_host_get_windows) fetches the next one.  At depth 1 the copy is kept until the next run, as the reference's getHitsFromFinishedRun can be
 // called again and again.
 int havac_host_next_run(havac_host *h) {
-    if (h->depth > 1) h->haveHits = h->haveWindows = false;
+    if (h->depth > 1) h->haveHits = h->haveWindows = h->haveDeviceWindows = false;
     return HAVAC_OK;
 }
 int havac_host_set_both_strands(havac_host *h, int on) { return guarded(h, [&] { h->obj->setBothStrands(on != 0); }); }
@@ -171,6 +174,40 @@ int havac_host_get_windows(havac_host *h, uint32_t flank, uint32_t *si, uint32_t
         h->windowsFlank = flank;
     }
     return copyWindows(h->windows, si, pi, rs, start, end, pf, pl, hc, cap, count);
+}
+
+int havac_host_set_window_chunk(havac_host *h, uint64_t records) { return guarded(h, [&] { h->obj->setWindowChunk(records); }); }
+int havac_host_window_scratch_bytes(havac_host *h, uint64_t *bytes) {
+    if (!bytes) return HAVAC_E_ARGUMENT;
+    return guarded(h, [&] { *bytes = h->obj->windowScratchBytes(); });
+}
+
+int havac_host_windows_of_records(const uint64_t *raw, uint64_t nraw, const uint64_t *recordEnds, uint32_t nrecords,
+                                  const uint32_t *modelLengths, uint32_t nmodels, uint32_t flank, uint32_t *si, uint32_t *pi,
+                                  uint8_t *rs, uint64_t *start, uint64_t *end, uint32_t *pf, uint32_t *pl, uint32_t *hc, uint32_t cap,
+                                  uint32_t *count) {
+    if ((nraw && !raw) || (nrecords && !recordEnds) || (nmodels && !modelLengths)) return HAVAC_E_ARGUMENT;
+    try {
+        vector<HavacWindow> w = havacWindowsOfRecords(vector<uint64_t>(raw, raw + nraw), vector<uint64_t>(recordEnds, recordEnds + nrecords),
+                                                      vector<uint32_t>(modelLengths, modelLengths + nmodels), flank);
+        if (w.size() > 0xffffffffull) return HAVAC_E_HIT_OVERFLOW;
+        return copyWindows(w, si, pi, rs, start, end, pf, pl, hc, cap, count);
+    } catch (const std::bad_alloc &) {
+        return HAVAC_E_NOMEM;
+    }
+}
+
+int havac_host_get_device_windows(havac_host *h, uint32_t flank, uint32_t *si, uint32_t *pi, uint8_t *rs, uint64_t *start,
+                                  uint64_t *end, uint32_t *pf, uint32_t *pl, uint32_t *hc, uint32_t cap, uint32_t *count) {
+    if (!h->haveDeviceWindows || h->deviceWindowsFlank != flank) {
+        h->deviceWindows.clear();
+        h->haveDeviceWindows = false;
+        int rc = guarded(h, [&] { h->deviceWindows = h->obj->getDeviceWindowsFromFinishedRun(flank); });
+        if (rc != HAVAC_OK) return rc;
+        h->haveDeviceWindows = true;
+        h->deviceWindowsFlank = flank;
+    }
+    return copyWindows(h->deviceWindows, si, pi, rs, start, end, pf, pl, hc, cap, count);
 }
 
 int havac_host_merge_windows(const uint64_t *sp, const uint32_t *sidx, const uint32_t *pp, const uint32_t *pidx,

@@ -62,6 +62,12 @@ HOST_SIGNATURES = {
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     "havac_host_get_windows": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
                                          C.POINTER(C.c_uint32)]),
+    "havac_host_set_window_chunk": (C.c_int, [_vp, C.c_uint64]),
+    "havac_host_window_scratch_bytes": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "havac_host_windows_of_records": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32] + [_vp] * 8 +
+                                      [C.c_uint32, C.POINTER(C.c_uint32)]),
+    "havac_host_get_device_windows": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
+                                                C.POINTER(C.c_uint32)]),
 }
 
 _host = None
@@ -189,6 +195,25 @@ class Havac:
         self._check(self._L.havac_host_get_windows(self._h, flank, *[a.ctypes.data for a in arrays], n.value, C.byref(n)))
         self._L.havac_host_next_run(self._h)      # (several runs open: the next call fetches the next run)
         return _windows_from_arrays(arrays, n.value)
+
+    def getDeviceWindowsFromFinishedRun(self, flank: int = 0):
+        """Not in the reference: the same windows as getWindowsFromFinishedRun, made on the GPU(s); no record is read back."""
+        n = C.c_uint32(0)
+        self._check(self._L.havac_host_get_device_windows(self._h, flank, *([None] * 8), 0, C.byref(n)))
+        arrays = _window_arrays(n.value)
+        self._check(self._L.havac_host_get_device_windows(self._h, flank, *[a.ctypes.data for a in arrays], n.value, C.byref(n)))
+        self._L.havac_host_next_run(self._h)      # (several runs open: the next call fetches the next run)
+        return _windows_from_arrays(arrays, n.value)
+
+    def setWindowChunk(self, records: int):
+        """records per chunk of the device window merge (0: the default); havac_dev_set_window_chunk on this object's handle"""
+        self._check(self._L.havac_host_set_window_chunk(self._h, records))
+
+    def windowScratchBytes(self) -> int:
+        """the most device memory the window merges of one GPU have held (havac_dev_window_stats)"""
+        n = C.c_uint64(0)
+        self._check(self._L.havac_host_window_scratch_bytes(self._h, C.byref(n)))
+        return n.value
 
     def rawHits(self) -> np.ndarray:
         n = C.c_uint32(0)

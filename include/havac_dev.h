@@ -202,6 +202,47 @@ int havac_dev_num_hits64(havac_dev *dev, uint64_t *count);
 int havac_dev_read_hits64(havac_dev *dev, uint64_t *out, uint64_t n);
 int havac_dev_read_hits(havac_dev *dev, uint64_t *out, uint32_t n);
 
+/* Optional, not in the reference (row f3: Havac::getDeviceWindowsFromFinishedRun).  The windows of the oldest open run, made on
+ * the GPU(s) that hold its records: every record is resolved against the tables given here, turned into the stretch of its record
+ * the model covers along the hit's diagonal widened by `flank`, and stretches of one (record, strand, model) that overlap or touch
+ * are merged -- element for element what havacMergeHitsToWindows (havac_amd/csrc/host/Havac.hpp) gives on the resolved hits, in
+ * its order: record, strand (forward first), model, start.  Only the windows cross PCIe.
+ *   record_ends     the FASTA end position (one past the terminator) of each of the nrecords records
+ *   model_lengths   rows of each of the nmodels models (nmodels < 2^24)
+ *   record_starts, record_columns, model_starts
+ *                   boundary mode: each record's first column and its columns (residues + terminator), each model's first row;
+ *                   all three NULL for the plain layout (records back to back, models back to back)
+ *   forward_columns both strands: columns of the forward half (columns from there on are the reverse strand); 0 for one strand
+ * Errors as havac_dev_num_hits64: HAVAC_E_HIT_OVERFLOW for an overflowed run, HAVAC_E_LOGIC for an aborted one, an error with no
+ * open run.  *count = the windows (64 bits).  The run is not closed (havac_dev_retire does that).  Records are taken in chunks of at
+ * most havac_dev_set_window_chunk records, so the device memory this needs beyond the tables does not grow with the run's list; the
+ * chunks' windows, and with several GPUs each GPU's, are joined on the host. */
+int havac_dev_compute_windows(havac_dev *dev, const uint64_t *record_ends, uint32_t nrecords, const uint32_t *model_lengths,
+                              uint32_t nmodels, const uint64_t *record_starts, const uint64_t *record_columns,
+                              const uint32_t *model_starts, uint64_t forward_columns, uint32_t flank, uint64_t *count);
+/* Copies the next min(n, windows not yet copied) windows of the last havac_dev_compute_windows into arrays matching HavacWindow's
+ * fields (sequenceIndex, phmmIndex, reverseStrand, sequenceStart, sequenceEnd, phmmFirst, phmmLast, hitCount); *copied = how many.
+ * Each call goes on where the last one stopped, and the library frees its host copy of what has been copied, so that the list and
+ * the caller's copy are never both whole in host memory: read a long list in slices.  HAVAC_E_LOGIC when the windows are not the
+ * oldest open run's (the run was closed since, or none were computed). */
+int havac_dev_read_windows(havac_dev *dev, uint64_t n, uint32_t *sequence_index, uint32_t *phmm_index, uint8_t *reverse_strand,
+                           uint64_t *sequence_start, uint64_t *sequence_end, uint32_t *phmm_first, uint32_t *phmm_last,
+                           uint32_t *hit_count, uint64_t *copied);
+/* Records per chunk of havac_dev_compute_windows (0: the default, 2^24; at most 2^31).  Small chunks are for tests: every chunk
+ * boundary is a join. */
+int havac_dev_set_window_chunk(havac_dev *dev, uint64_t records);
+/* *scratch_bytes (may be NULL): the most device memory the window merges of any one GPU of the handle have held -- per-chunk
+ * scratch, rocPRIM's temporary storage and the resolve tables.  *read_back_bytes (may be NULL): the bytes of windows the last
+ * havac_dev_compute_windows copied from the GPUs (every chunk's windows, 40 B each, before they are joined). */
+int havac_dev_window_stats(havac_dev *dev, uint64_t *scratch_bytes, uint64_t *read_back_bytes);
+/* The host join havac_dev_compute_windows applies to its chunks and GPUs, on its own (no device needed): `nlists` window lists
+ * lie back to back in the eight arrays (list l ends at list_ends[l]; the last end == nwindows), each sorted and merged as
+ * havacMergeHitsToWindows leaves its output (phmm_index < 2^24).  They are joined in place into one such list; *count = its
+ * length. */
+int havac_windows_join(uint64_t nwindows, const uint64_t *list_ends, uint32_t nlists, uint32_t *sequence_index, uint32_t *phmm_index,
+                       uint8_t *reverse_strand, uint64_t *sequence_start, uint64_t *sequence_end, uint32_t *phmm_first,
+                       uint32_t *phmm_last, uint32_t *hit_count, uint64_t *count);
+
 /* Device time of the last completed run in milliseconds (HIP events on the
  * handle's stream): the SSV kernel alone, and the whole enqueue (model
  * padding copy + SSV + hit ordering). */

@@ -117,6 +117,22 @@ int havac_host_merge_windows(const uint64_t *sequence_position, const uint32_t *
 int havac_host_get_windows(havac_host *h, uint32_t flank, uint32_t *w_sequence_index, uint32_t *w_phmm_index,
                            uint8_t *w_reverse_strand, uint64_t *w_start, uint64_t *w_end, uint32_t *w_phmm_first,
                            uint32_t *w_phmm_last, uint32_t *w_hit_count, uint32_t cap, uint32_t *count);
+/* The same windows made on the GPU(s) that hold the run's records (Havac::getDeviceWindowsFromFinishedRun): no record is read
+ * back, and havac_host_get_raw_hits reports none afterwards.  Fetched once and served from a copy, with the same count-then-arrays
+ * and havac_host_next_run rules as havac_host_get_windows (the two keep separate copies). */
+int havac_host_get_device_windows(havac_host *h, uint32_t flank, uint32_t *w_sequence_index, uint32_t *w_phmm_index,
+                                  uint8_t *w_reverse_strand, uint64_t *w_start, uint64_t *w_end, uint32_t *w_phmm_first,
+                                  uint32_t *w_phmm_last, uint32_t *w_hit_count, uint32_t cap, uint32_t *count);
+/* Havac::setWindowChunk / windowScratchBytes: records per chunk of that merge (0: the default), and the most device memory one
+ * GPU's merges have held (include/havac_dev.h: havac_dev_set_window_chunk, havac_dev_window_stats) */
+int havac_host_set_window_chunk(havac_host *h, uint64_t records);
+int havac_host_window_scratch_bytes(havac_host *h, uint64_t *bytes);
+/* Havac.hpp: havacWindowsOfRecords -- the host path of havac_host_get_windows after its read-back (plain layout, one strand) on
+ * explicit tables: raw records, FASTA record ends, model lengths.  Output as havac_host_merge_windows.  (Checking and timing aid.) */
+int havac_host_windows_of_records(const uint64_t *raw, uint64_t nraw, const uint64_t *record_ends, uint32_t nrecords,
+                                  const uint32_t *model_lengths, uint32_t nmodels, uint32_t flank, uint32_t *w_sequence_index,
+                                  uint32_t *w_phmm_index, uint8_t *w_reverse_strand, uint64_t *w_start, uint64_t *w_end,
+                                  uint32_t *w_phmm_first, uint32_t *w_phmm_last, uint32_t *w_hit_count, uint32_t cap, uint32_t *count);
 
 #ifdef __cplusplus
 }
