@@ -53,6 +53,15 @@ SIGNATURES = {
     "havac_dev_set_window_chunk": (C.c_int, [_vp, C.c_uint64]),
     "havac_dev_window_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "havac_windows_join": (C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.POINTER(C.c_uint64)]),
+    "havac_stream_block": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64] + [C.POINTER(C.c_uint64)] * 4),
+    "havac_dev_stream_open": (C.c_int, [_vp]),
+    "havac_dev_stream_close": (C.c_int, [_vp]),
+    "havac_dev_stream_submit_text": (C.c_int, [_vp, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_uint64] * 5),
+    "havac_dev_stream_submit_records": (C.c_int, [_vp, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p,
+                                                  C.POINTER(C.c_uint64)]),
+    "havac_dev_stream_collect": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "havac_dev_stream_read_hits": (C.c_int, [_vp, C.c_void_p, C.c_uint64]),
+    "havac_dev_stream_in_flight": (C.c_uint32, [_vp]),
     "havac_dev_last_run_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "havac_dev_last_error": (C.c_char_p, [_vp]),
     "havac_ssv_ctx_create": (C.c_int, [C.POINTER(C.c_void_p)]),
@@ -61,6 +70,7 @@ SIGNATURES = {
                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "havac_ssv_shard_window": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "havac_ssv_set_sequence_window": (C.c_int, [_vp, C.c_uint64, C.c_uint64]),
+    "havac_ssv_set_owned_columns": (C.c_int, [_vp, C.c_uint64, C.c_uint64]),
     "havac_ssv_set_separator_mask": (C.c_int, [_vp, C.c_void_p]),
     "havac_ssv_set_order_stream": (C.c_int, [_vp, C.c_void_p]),
     "havac_ssv_set_cell_trace": (C.c_int, [_vp, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32]),

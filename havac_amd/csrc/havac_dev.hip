@@ -83,6 +83,27 @@ void shard_window(uint64_t nsymbols, uint32_t nrows, uint64_t col_begin, uint64_
     *end = std::min<uint64_t>(nsymbols, (hi + HAVAC_SEGMENT_COLUMNS - 1) / HAVAC_SEGMENT_COLUMNS * HAVAC_SEGMENT_COLUMNS);
 }
 
+// The hit record's segment field is 26 bits wide ([39:14]): the most segments a database -- one load or a stream -- can have.
+constexpr uint64_t kMaxSegments = 1ull << 26;
+
+// A streamed search (havac_stream_block): block k owns columns [k B, (k+1) B) of the database's N (padded) columns; its pass
+// reads what shard_window names for that range.  nsymbols == 0: N is not known yet, and the block is not the database's end --
+// the look-ahead is then what shard_window adds on the right, as if the database went on.
+int stream_block(uint64_t block_columns, uint32_t nrows, uint64_t k, uint64_t nsymbols, uint64_t* own_begin, uint64_t* own_end,
+                 uint64_t* first, uint64_t* end) {
+    if (block_columns == 0 || block_columns % HAVAC_SEGMENT_COLUMNS != 0 || nrows == 0 || nsymbols % HAVAC_SEGMENT_COLUMNS != 0)
+        return HAVAC_E_ARGUMENT;
+    if (k > kMaxSegments * HAVAC_SEGMENT_COLUMNS / block_columns) return HAVAC_E_LENGTH;
+    const uint64_t b = k * block_columns;
+    if (nsymbols && b >= nsymbols) return HAVAC_E_ARGUMENT;                  // no such block
+    const uint64_t e = nsymbols ? std::min(nsymbols, b + block_columns) : b + block_columns;
+    const uint64_t known = nsymbols ? nsymbols : e + 2 * kTileDiags + HAVAC_SEGMENT_COLUMNS;
+    if (e / HAVAC_SEGMENT_COLUMNS > kMaxSegments || (nsymbols && nsymbols / HAVAC_SEGMENT_COLUMNS > kMaxSegments)) return HAVAC_E_LENGTH;
+    *own_begin = b; *own_end = e;
+    shard_window(known, nrows, b, e, first, end);
+    return HAVAC_OK;
+}
+
 // ---- partitions of a launch's units ----------------------------------------------------------------------------------------
 struct PartitionKey {
     uint64_t nsymbols = 0; uint32_t nrows = 0; uint64_t col_begin = 0, col_end = 0; uint32_t tb = 0, te = 0, parts_log2 = 0;
@@ -339,6 +360,7 @@ struct havac_ssv_ctx {
     CellRecord* trace_cells = nullptr; uint32_t trace_row0 = 0, trace_rows = 0, trace_cols = 0; uint64_t trace_col0 = 0;   // per-cell trace window (debugging)
     hipStream_t order_stream = nullptr;        // optional: where finish() orders the records (default: the enqueue's stream)
     uint64_t window_first = 0, window_columns = 0;   // the caller's sequence buffer holds only these columns (0, 0: all of them)
+    uint64_t own_begin = 0, own_end = 0;             // havac_ssv_set_owned_columns: the pass owns these columns (0, 0: its shard's)
     // experiment knobs (havac_ssv_set_tuning): -1 = the library decides
     int tune_rows_per_block = -1, tune_tiles_per_item = -1, tune_block_tails = -1;
     int tune_variant = -1;                     // havac_ssv_set_kernel_variant: -1 the library decides, 0 standard kernel, 1 resident-table kernel where valid
@@ -574,6 +596,33 @@ static int check_inputs(std::string& err, uint64_t nsymbols, uint32_t nrows) {
     return HAVAC_OK;
 }
 
+// the limits of a pass over an owned range: one shard, whole segments inside the hit record's 26-bit segment field, and a
+// window (what the caller's buffer holds) below the reference's 4 GiB
+static int check_owned(havac_ssv_ctx* c, uint64_t nsymbols, uint32_t nrows, uint32_t shard_count) {
+    if (shard_count != 1) { c->err = "a pass over an owned column range is one shard (shard 0 of 1)"; return HAVAC_E_ARGUMENT; }
+    if (int rc = check_inputs(c->err, HAVAC_SEGMENT_COLUMNS, nrows)) return rc;
+    if (nsymbols % HAVAC_SEGMENT_COLUMNS != 0 || nsymbols < c->own_end) {
+        c->err = "the columns known (" + std::to_string(nsymbols) + ") must be whole segments and reach the owned range's end (" +
+                 std::to_string(c->own_end) + ")";
+        return HAVAC_E_LENGTH;
+    }
+    if (nsymbols / HAVAC_SEGMENT_COLUMNS > kMaxSegments) { c->err = "more segments than the hit record's 26-bit segment field holds"; return HAVAC_E_LENGTH; }
+    const uint64_t held = c->window_columns ? c->window_columns : nsymbols;
+    if (held / 4 >= (4ull << 30)) { c->err = "compressed sequence size must be less than 4GiB"; return HAVAC_E_LENGTH; }
+    return HAVAC_OK;
+}
+
+extern "C" int havac_ssv_set_owned_columns(havac_ssv_ctx* c, uint64_t col_begin, uint64_t col_end) {
+    if (!c) return HAVAC_E_ARGUMENT;
+    if (c->pending) { c->err = "a pass is in flight: set the owned columns between passes"; return HAVAC_E_LOGIC; }
+    if (col_begin % HAVAC_SEGMENT_COLUMNS != 0 || col_end % HAVAC_SEGMENT_COLUMNS != 0 || (col_end && col_end <= col_begin)) {
+        c->err = "an owned range is a non-empty run of whole 12288-column segments";
+        return HAVAC_E_ARGUMENT;
+    }
+    c->own_begin = col_end ? col_begin : 0; c->own_end = col_end;
+    return HAVAC_OK;
+}
+
 extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, uint64_t nsymbols,
                                  const int8_t* d_phmm, uint32_t nrows, uint32_t shard_index,
                                  uint32_t shard_count, uint64_t* d_hits, uint64_t hit_capacity,
@@ -588,7 +637,10 @@ extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, ui
         return HAVAC_E_ARGUMENT;
     }
     if (c->pending) { c->err = "previous pass not finished: call havac_ssv_finish first"; return HAVAC_E_LOGIC; }
-    int rc = check_inputs(c->err, nsymbols, nrows);
+    // an owned range (a streamed search, havac_ssv_set_owned_columns): nsymbols counts the columns known so far and may pass the
+    // 4 GiB of one buffer -- the window the caller's buffer holds may not; otherwise the reference's limits
+    const bool owned = c->own_end != 0;
+    int rc = owned ? check_owned(c, nsymbols, nrows, shard_count) : check_inputs(c->err, nsymbols, nrows);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     HIP_TRY(c->err, hipSetDevice(c->device));
@@ -599,7 +651,8 @@ extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, ui
     const uint32_t flag_words = (t.nrows_padded / kChunkRows + 1 + 3) / 4 + 2;     // a byte per chunk; + 2: the kernels load a word ahead
     if (c->chunk_flags.capacity() < flag_words) HIP_TRY(c->err, c->chunk_flags.grow(flag_words));
     uint64_t col_begin, col_end;
-    shard_columns(nsymbols, shard_index, shard_count, &col_begin, &col_end);
+    if (owned) { col_begin = c->own_begin; col_end = c->own_end; }
+    else shard_columns(nsymbols, shard_index, shard_count, &col_begin, &col_end);
     uint32_t tb, te;
     shard_tiles(t, nrows, col_begin, col_end, &tb, &te);
     if (c->window_columns) {
@@ -620,6 +673,7 @@ extern "C" int havac_ssv_enqueue(havac_ssv_ctx* c, const uint8_t* d_sequence, ui
     unsigned row_bits = 1, seg_bits = 1;
     while ((1u << row_bits) < t.nrows_padded + 2u) row_bits++;
     while ((1ull << seg_bits) < nsymbols / HAVAC_SEGMENT_COLUMNS) seg_bits++;
+    if (14 + row_bits + seg_bits > 64) { c->err = "the segment and row fields do not fit one 64-bit sort key"; return HAVAC_E_LENGTH; }
     // ---- how the tiles are handed out (plan_launch; ssv_kernels.hip.h, "items") ----
     SsvRare L{};          // the kernel's first argument: tiling, hit queue, hand-off buffers (read from the kernarg segment on demand)
     const uint64_t slots = (uint64_t)c->resident_blocks * kWavesPerBlock;
@@ -1023,6 +1077,29 @@ struct Run {
 };
 
 constexpr uint32_t kMaxDepth = 4;
+
+// A streamed search (havac_dev_stream_*): a pipe of its own with two passes in flight, and two block buffers that alternate --
+// block k + 1 is carried, uploaded and packed into one while the pass of block k reads the other.  Nothing of what the handle's
+// own entry points loaded (d_seq, d_mask, the handle's pipe and its open runs) is touched.
+struct StreamState {
+    int device = 0;
+    havac_pipe* pipe = nullptr;
+    hipStream_t stream = nullptr;                  // carries, uploads and packing of the blocks
+    DeviceBuffer<uint8_t> seq[2], mask[2];         // the block buffers (mask: boundary mode)
+    DeviceBuffer<char> text;                       // the block's text on its way to the packing kernel
+    uint64_t first[2] = {0, 0}, end[2] = {0, 0};   // plain mode: the columns buffer b holds
+    uint32_t next = 0;                             // the buffer of the next block
+    uint64_t blocks = 0;                           // blocks submitted
+    const uint64_t* records = nullptr;             // the records of the last collected pass (device memory of the pipe's slot)
+    uint64_t nrecords = 0;
+    ~StreamState() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (pipe) havac_pipe_destroy(pipe);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 struct havac_dev {
     std::vector<DevicePart> parts;
     uint64_t seq_bytes = 0, phmm_bytes = 0, mask_bytes = 0;
@@ -1038,6 +1115,7 @@ struct havac_dev {
     WindowBlocks windows;
     bool have_windows = false;
     uint64_t windows_run = 0, window_chunk = 0, windows_read_back = 0;
+    struct StreamState* stream = nullptr;     // an open streamed search (havac_dev_stream_open), on the first GPU
 };
 
 // the reference's fixed hit buffer: 14 * 256 MiB = 3.5 GiB = 469,762,048 records (host/HavacHwClient.hpp:94)
@@ -1119,6 +1197,7 @@ extern "C" void havac_dev_destroy(havac_dev* d) {
         if (p.abort_stream) (void)hipStreamDestroy(p.abort_stream);
         if (p.stream) (void)hipStreamDestroy(p.stream);
     }
+    (void)havac_dev_stream_close(d);
     delete d;          // (the parts' device memory: ~DevicePart)
 }
 
@@ -1836,5 +1915,216 @@ extern "C" int havac_windows_join(uint64_t nwindows, const uint64_t* list_ends, 
     } catch (const std::bad_alloc&) {
         return HAVAC_E_NOMEM;
     }
+    return HAVAC_OK;
+}
+
+// ===========================================================================
+// Level 1b: a streamed search (Havac::searchFastaFile)
+// ===========================================================================
+extern "C" int havac_stream_block(uint64_t block_columns, uint32_t nrows, uint64_t block_index, uint64_t nsymbols, uint64_t* own_begin,
+                                  uint64_t* own_end, uint64_t* first_column, uint64_t* end_column) {
+    if (!own_begin || !own_end || !first_column || !end_column) return HAVAC_E_ARGUMENT;
+    return stream_block(block_columns, nrows, block_index, nsymbols, own_begin, own_end, first_column, end_column);
+}
+
+extern "C" int havac_dev_stream_open(havac_dev* d) {
+    if (!d) return HAVAC_E_ARGUMENT;
+    if (any_unfinished(d)) { d->err = "a run is in flight: finish it before a streamed search"; return HAVAC_E_LOGIC; }
+    if (d->phmm_bytes == 0) { d->err = "no model is loaded: load one before a streamed search"; return HAVAC_E_LOGIC; }
+    (void)havac_dev_stream_close(d);
+    DevicePart& p = d->parts[0];
+    HIP_TRY(d->err, hipSetDevice(p.device));
+    StreamState* s = new (std::nothrow) StreamState;
+    if (!s) return HAVAC_E_NOMEM;
+    s->device = p.device;
+    d->stream = s;
+    HIP_TRY(d->err, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if (int rc = havac_pipe_create(2, d->hit_capacity, -1, &s->pipe)) {
+        d->err = "could not allocate the hit buffers and contexts of a streamed search's two passes";
+        return rc;
+    }
+    const int* v = d->tuning;                       // the handle's experiment knobs hold for its streamed passes too
+    for (int k = 0; k < 2; k++) {
+        havac_ssv_ctx* const ctx = havac_pipe_context(s->pipe, k);
+        int rc = havac_ssv_set_tuning(ctx, v[0], v[1], v[2], v[3]);
+        if (!rc) rc = havac_ssv_set_split_tuning(ctx, v[4], v[5], v[6], v[7]);
+        if (!rc) rc = havac_ssv_set_kernel_variant(ctx, v[8]);
+        if (rc) { d->err = havac_ssv_ctx_last_error(ctx); return rc; }
+    }
+    return HAVAC_OK;
+}
+
+static int stream_ready(havac_dev* d) {
+    if (!d->stream) { d->err = "no streamed search is open (havac_dev_stream_open)"; return HAVAC_E_LOGIC; }
+    if (d->phmm_bytes == 0) { d->err = "phmm length in vectors cannot be 0, but 0 was given to the client."; return HAVAC_E_LENGTH; }
+    if (havac_pipe_in_flight(d->stream->pipe) == havac_pipe_depth(d->stream->pipe)) {
+        d->err = "both passes of the streamed search are in flight: collect the older one first";
+        return HAVAC_E_LOGIC;
+    }
+    return HAVAC_OK;
+}
+
+// hands buffer b to the next pass of the stream's pipe: `nsymbols` columns known, the buffer holding [window_first,
+// window_first + window_columns) (0, 0: all), owning [own_begin, own_end) (0, 0: all)
+static int stream_submit(havac_dev* d, uint32_t b, uint64_t nsymbols, uint64_t window_first, uint64_t window_columns, uint64_t own_begin,
+                         uint64_t own_end, const uint8_t* mask) {
+    StreamState* s = d->stream;
+    havac_ssv_ctx* const ctx = havac_pipe_context(s->pipe, -2);       // the slot the pass will take
+    int rc = havac_ssv_set_separator_mask(ctx, mask);
+    if (!rc) rc = havac_ssv_set_sequence_window(ctx, window_first, window_columns);
+    if (!rc) rc = havac_ssv_set_owned_columns(ctx, own_begin, own_end);
+    if (rc) { d->err = havac_ssv_ctx_last_error(ctx); return rc; }
+    rc = havac_pipe_submit(s->pipe, s->seq[b].get(), nsymbols, d->parts[0].d_phmm.get(), (uint32_t)(d->phmm_bytes / 4), 0, 1, nullptr,
+                           HAVAC_NO_STREAM);
+    if (rc) { d->err = havac_pipe_last_error(s->pipe); return rc; }
+    s->next = b ^ 1u;
+    s->blocks++;
+    return HAVAC_OK;
+}
+
+extern "C" int havac_dev_stream_submit_text(havac_dev* d, const char* chars, uint64_t nchars, const uint64_t* patch_columns,
+                                            const uint8_t* patch_symbols, uint64_t npatches, uint64_t first_column, uint64_t end_column,
+                                            uint64_t own_begin, uint64_t own_end, uint64_t nsymbols) {
+    if (!d || (!chars && nchars) || (npatches && (!patch_columns || !patch_symbols))) return HAVAC_E_ARGUMENT;
+    if (int rc = stream_ready(d)) return rc;
+    StreamState* s = d->stream;
+    const uint32_t b = s->next, a = b ^ 1u;
+    // columns before `from` are packed already, in buffer a (the block before); this block's text is [from, from + nchars)
+    const uint64_t from = s->blocks ? s->end[a] : 0;
+    const uint64_t S = HAVAC_SEGMENT_COLUMNS;
+    if (first_column % S || end_column % S || own_begin % S || own_end % S || nsymbols % S || first_column > own_begin ||
+        own_begin >= own_end || own_end > end_column || end_column > nsymbols || from > end_column || first_column > from ||
+        (s->blocks && first_column < s->first[a]) || nchars > end_column - from) {
+        d->err = "a streamed block must own whole segments inside its buffer [first, end), start its buffer at or after the block "
+                 "before's, and bring the text of the columns from where the block before's buffer ended";
+        return HAVAC_E_ARGUMENT;
+    }
+    for (uint64_t i = 0; i < npatches; i++)
+        if (patch_columns[i] < from || patch_columns[i] >= end_column || (i && patch_columns[i] <= patch_columns[i - 1])) {
+            d->err = "patch columns must be ascending and inside the columns this block packs";
+            return HAVAC_E_ARGUMENT;
+        }
+    if ((end_column - first_column) / 4 >= (4ull << 30)) { d->err = "a streamed block's buffer must be below 4GiB"; return HAVAC_E_LENGTH; }
+    HIP_TRY(d->err, hipSetDevice(s->device));
+    const hipStream_t st = s->stream;
+    const uint64_t nbytes = (end_column - first_column) / 4;
+    if (s->seq[b].capacity() < nbytes) HIP_TRY(d->err, s->seq[b].grow(nbytes + nbytes / 8));
+    uint8_t* const seq = s->seq[b].get();
+    // halo and look-ahead: the columns the block before packed move device to device (never packed twice: rand() is drawn once
+    // per column, in file order)
+    if (from > first_column)
+        HIP_TRY(d->err, hipMemcpyAsync(seq, s->seq[a].get() + (first_column - s->first[a]) / 4, (from - first_column) / 4,
+                                       hipMemcpyDeviceToDevice, st));
+    DeviceBuffer<uint64_t> d_cols;
+    DeviceBuffer<uint8_t> d_syms;
+    if (end_column > from) {
+        // the new columns, packed from column `from` on (a multiple of 12288: whole 32-bit words); behind the text, symbol 0
+        uint32_t* const packed = reinterpret_cast<uint32_t*>(seq + (from - first_column) / 4);
+        if (nchars) {
+            if (s->text.capacity() < nchars) HIP_TRY(d->err, s->text.grow(nchars + nchars / 8));
+            HIP_TRY(d->err, hipMemcpyAsync(s->text.get(), chars, nchars, hipMemcpyHostToDevice, st));
+        }
+        const uint64_t words = (end_column - from) / 16;
+        hipLaunchKernelGGL(ssv_pack_chars, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<const uint8_t*>(s->text.get()), 0, nchars, end_column - from, packed);
+        if (npatches) {
+            std::vector<uint64_t> rel(patch_columns, patch_columns + npatches);
+            for (uint64_t& c : rel) c -= from;
+            HIP_TRY(d->err, d_cols.copy_from(rel.data(), rel.size(), st));
+            HIP_TRY(d->err, d_syms.copy_from(patch_symbols, npatches, st));
+            hipLaunchKernelGGL(ssv_patch_symbols, dim3((unsigned)((npatches + 255) / 256)), dim3(256), 0, st, d_cols.get(), d_syms.get(),
+                               npatches, packed);
+        }
+    }
+    HIP_TRY(d->err, hipStreamSynchronize(st));      // (the caller's text may go; the pass finds its buffer complete)
+    HIP_TRY(d->err, hipGetLastError());
+    s->first[b] = first_column; s->end[b] = end_column;
+    return stream_submit(d, b, nsymbols, first_column, end_column - first_column, own_begin, own_end, nullptr);
+}
+
+extern "C" int havac_dev_stream_submit_records(havac_dev* d, const char* chars, uint64_t nchars, const uint64_t* record_ends,
+                                               uint32_t nrecords, int both_strands, uint64_t* record_starts_out, uint64_t* forward_columns_out) {
+    if (!d || (!chars && nchars) || (nrecords && !record_ends) || nrecords == 0) return HAVAC_E_ARGUMENT;
+    if (int rc = stream_ready(d)) return rc;
+    StreamState* s = d->stream;
+    // the layout of havac_dev_write_sequence_records: record k at [start_k, start_k + len_k), then a separator pair at an even column
+    std::vector<uint64_t> starts(nrecords), begins(nrecords), lens(nrecords), residues(nrecords);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < nrecords; k++) {
+        const uint64_t begin = k ? record_ends[k - 1] : 0;
+        if (record_ends[k] <= begin || record_ends[k] > nchars) { d->err = "record ends must be ascending and inside the text"; return HAVAC_E_ARGUMENT; }
+        starts[k] = at; begins[k] = begin; lens[k] = record_ends[k] - begin; residues[k] = lens[k] - 1;
+        at += lens[k];
+        at += at & 1;
+        at += 2;
+    }
+    const uint64_t ncolumns = (at + HAVAC_SEGMENT_COLUMNS - 1) / HAVAC_SEGMENT_COLUMNS * HAVAC_SEGMENT_COLUMNS;
+    const uint64_t total = both_strands ? 2 * ncolumns : ncolumns, nbytes = total / 4;
+    if (nbytes >= (4ull << 30)) { d->err = "a streamed block's buffer must be below 4GiB"; return HAVAC_E_LENGTH; }
+    const uint32_t b = s->next;
+    HIP_TRY(d->err, hipSetDevice(s->device));
+    const hipStream_t st = s->stream;
+    if (s->seq[b].capacity() < nbytes) HIP_TRY(d->err, s->seq[b].grow(nbytes + nbytes / 8));
+    if (s->mask[b].capacity() < nbytes / 4) HIP_TRY(d->err, s->mask[b].grow(nbytes / 4 + nbytes / 32));
+    if (s->text.capacity() < nchars) HIP_TRY(d->err, s->text.grow(nchars + nchars / 8));
+    HIP_TRY(d->err, hipMemcpyAsync(s->text.get(), chars, nchars, hipMemcpyHostToDevice, st));
+    DeviceBuffer<uint64_t> d_starts, d_begins, d_lens, d_residues;
+    HIP_TRY(d->err, d_starts.copy_from(starts.data(), nrecords, st));
+    HIP_TRY(d->err, d_begins.copy_from(begins.data(), nrecords, st));
+    HIP_TRY(d->err, d_lens.copy_from(lens.data(), nrecords, st));
+    uint32_t* const packed = reinterpret_cast<uint32_t*>(s->seq[b].get());
+    hipLaunchKernelGGL(ssv_pack_records, dim3((unsigned)((ncolumns / 16 + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const uint8_t*>(s->text.get()), d_starts.get(), d_begins.get(), d_lens.get(), nrecords, at, ncolumns,
+                       packed, s->mask[b].get());
+    if (both_strands) {      // the second half as havac_dev_append_reverse_strand makes it; the separators repeat
+        HIP_TRY(d->err, d_residues.copy_from(residues.data(), nrecords, st));
+        hipLaunchKernelGGL(ssv_reverse_strand, dim3((unsigned)((ncolumns / 16 + 255) / 256)), dim3(256), 0, st, packed, ncolumns,
+                           d_starts.get(), d_residues.get(), nrecords);
+        HIP_TRY(d->err, hipMemcpyAsync(s->mask[b].get() + ncolumns / 16, s->mask[b].get(), ncolumns / 16, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(d->err, hipStreamSynchronize(st));
+    HIP_TRY(d->err, hipGetLastError());
+    if (record_starts_out) std::copy(starts.begin(), starts.end(), record_starts_out);
+    if (forward_columns_out) *forward_columns_out = both_strands ? ncolumns : 0;
+    s->first[b] = 0; s->end[b] = total;
+    return stream_submit(d, b, total, 0, 0, 0, 0, s->mask[b].get());
+}
+
+extern "C" uint32_t havac_dev_stream_in_flight(havac_dev* d) { return d && d->stream ? havac_pipe_in_flight(d->stream->pipe) : 0; }
+
+extern "C" int havac_dev_stream_collect(havac_dev* d, uint64_t* count) {
+    if (!d) return HAVAC_E_ARGUMENT;
+    if (!d->stream || havac_pipe_in_flight(d->stream->pipe) == 0) { d->err = "no streamed pass is in flight"; return HAVAC_E_LOGIC; }
+    StreamState* s = d->stream;
+    s->records = nullptr; s->nrecords = 0;
+    HIP_TRY(d->err, hipSetDevice(s->device));
+    uint64_t found = 0, n = 0;
+    const uint64_t* records = nullptr;
+    const int rc = havac_pipe_collect(s->pipe, &found, &records, &n, HAVAC_NO_STREAM);
+    if (count) *count = found;
+    if (rc) { d->err = havac_pipe_last_error(s->pipe); return rc; }
+    s->records = records; s->nrecords = n;
+    return HAVAC_OK;
+}
+
+extern "C" int havac_dev_stream_read_hits(havac_dev* d, uint64_t* out, uint64_t n) {
+    if (!d || (!out && n)) return HAVAC_E_ARGUMENT;
+    if (!d->stream) { d->err = "no streamed search is open"; return HAVAC_E_LOGIC; }
+    StreamState* s = d->stream;
+    if (n > s->nrecords) { d->err = "the last collected pass has fewer records than requested"; return HAVAC_E_LENGTH; }
+    if (n == 0) return HAVAC_OK;
+    HIP_TRY(d->err, hipSetDevice(s->device));
+    HIP_TRY(d->err, hipMemcpy(out, s->records, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return HAVAC_OK;
+}
+
+extern "C" int havac_dev_stream_close(havac_dev* d) {
+    if (!d) return HAVAC_E_ARGUMENT;
+    if (!d->stream) return HAVAC_OK;
+    StreamState* s = d->stream;
+    (void)hipSetDevice(s->device);
+    while (s->pipe && havac_pipe_in_flight(s->pipe)) (void)havac_pipe_collect(s->pipe, nullptr, nullptr, nullptr, HAVAC_NO_STREAM);
+    delete s;
+    d->stream = nullptr;
     return HAVAC_OK;
 }

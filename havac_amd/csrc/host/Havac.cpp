@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "../../../include/havac_dev.h"
+#include "FastaStream.h"
 #include "HostThreads.hpp"
 #include "PhmmPreprocessor.hpp"
 #include "SequencePreprocessor.hpp"
@@ -339,6 +340,10 @@ vector<HavacHit> Havac::resolveRun(const RunInputs &run, uint64_t n, RunInputs *
     if (inputsOut) *inputsOut = run;
     rawHits_.assign(n, 0);
     if (n) check(havac_dev_read_hits64(dev_, rawHits_.data(), n));
+    return resolveRaw(rawHits_, run, boundaryMode_);
+}
+
+vector<HavacHit> Havac::resolveRaw(const vector<uint64_t> &raw, const RunInputs &run, bool boundaryMode) {
     // both strands: a record of the second half is the record at (column - forwardColumns) of the first.  Folded record by
     // record where it is resolved: no second copy of the list and no flag per record (with one strand -- the reference's
     // mode -- nothing at all is done: C4's list is 36 GB)
@@ -353,14 +358,13 @@ vector<HavacHit> Havac::resolveRun(const RunInputs &run, uint64_t n, RunInputs *
         *isReverse = true;
         return (rec & ~((1ull << 40) - 1)) | ((column / 12288ull) << 14) | (column % 12288ull);
     };
-    const vector<uint64_t> &raw = rawHits_;
     auto mirror = [&](HavacHit &h, bool isReverse) {
         if (!isReverse) return;
         h.reverseStrand = true;
         const uint64_t n = run.residueCounts[h.sequenceIndex];
         if (h.sequencePosition < n) h.sequencePosition = n - 1 - h.sequencePosition;   // the terminator column stays
     };
-    if (!boundaryMode_) {
+    if (!boundaryMode) {
         return resolveAll(raw.size(), [&](size_t i, HavacHit *hit) {
             bool isReverse;
             if (!resolveOne(fold(raw[i], &isReverse), i, run.recordEnds, run.prefixSums, hit)) return false;
@@ -499,6 +503,145 @@ vector<HavacWindow> Havac::getDeviceWindowsFromFinishedRun(uint32_t flank) {
         }
         return out;
     });
+}
+
+// ---- a streamed search ---------------------------------------------------------------------------------------------------
+vector<HavacHit> Havac::searchFastaFile(const std::string &path, uint64_t blockColumns,
+                                        std::function<void(const vector<HavacHit> &)> onBlock) {
+    if (!phmmLoadedToDevice) throw std::logic_error("Phmm was not loaded to device before a search was requested.");
+    if (bothStrands_ && !boundaryMode_)
+        throw std::logic_error("a streamed search in the plain layout cannot score both strands: in one load the reverse half directly "
+                               "follows the forward half, so a diagonal runs from the database's last forward columns into its first "
+                               "reverse columns, which one pass over the file cannot reproduce; search both strands in boundary mode");
+    const uint64_t S = HAVAC_SEGMENT_COLUMNS;
+    if (blockColumns == 0) blockColumns = kDefaultSearchBlockColumns;
+    blockColumns = (blockColumns + S - 1) / S * S;
+    searchStats_ = HavacSearchStats();
+    FastaStreamReader reader(path);
+    needDevice();
+    check(havac_dev_stream_open(dev_));
+    struct CloseStream {
+        havac_dev *d;
+        ~CloseStream() { (void)havac_dev_stream_close(d); }
+    } closeStream{dev_};
+
+    // the tables a block's records are resolved against (RunInputs: the plain mode's record ends grow as the reader goes)
+    RunInputs tables;
+    tables.prefixSums = generatePhmmLenPrefixSums();
+    for (uint32_t i = 0; i < p7HmmList->count; i++) tables.lengths.push_back(p7HmmList->phmms[i].header.modelLength);
+    tables.starts = modelStarts_;
+    // a block in flight: its text columns (plain mode: the columns its pass owns), its first record, its tables (boundary mode)
+    struct Block { uint64_t index, ownBegin, ownEnd, firstRecord; RunInputs boundary; };
+    std::deque<Block> inFlight;
+    vector<HavacHit> all;
+    HavacSearchStats &stats = searchStats_;
+    vector<uint64_t> raw;
+    auto collect = [&] {
+        Block b = std::move(inFlight.front());
+        inFlight.pop_front();
+        uint64_t n = 0;
+        const int rc = havac_dev_stream_collect(dev_, &n);
+        if (rc == HAVAC_E_HIT_OVERFLOW)
+            throw std::overflow_error("block " + std::to_string(b.index) + " of the search (columns " + std::to_string(b.ownBegin) + " to " +
+                                      std::to_string(b.ownEnd) + ") found " + std::to_string(n) + " hits, more than the hit capacity of " +
+                                      "a pass holds (setHitCapacity)");
+        check(rc);
+        raw.assign(n, 0);
+        if (n) check(havac_dev_stream_read_hits(dev_, raw.data(), n));
+        vector<HavacHit> hits;
+        if (!boundaryMode_) {
+            // records that end behind what the reader has read are not known yet: a column past the last known end belongs to the
+            // record being read (a sentinel end), not to the padding -- until the file has been read to its end
+            const bool open = !reader.atEnd();
+            if (open) tables.recordEnds.push_back(UINT64_MAX);
+            hits = resolveRaw(raw, tables, false);
+            if (open) tables.recordEnds.pop_back();
+        } else {
+            hits = resolveRaw(raw, b.boundary, true);
+            for (HavacHit &h : hits) h.sequenceIndex += (uint32_t)b.firstRecord;
+        }
+        if (onBlock) { onBlock(hits); return; }
+        stats.rawHits.insert(stats.rawHits.end(), raw.begin(), raw.end());
+        all.insert(all.end(), hits.begin(), hits.end());
+    };
+    auto noteRecords = [&] {
+        uint64_t start = tables.recordEnds.empty() ? 0 : tables.recordEnds.back();
+        for (const uint64_t end : reader.recordEnds()) {
+            stats.recordLengths.push_back(end - start - 1);
+            tables.recordEnds.push_back(end);
+            start = end;
+        }
+    };
+    auto planned = [&](uint64_t k, uint64_t nsymbols, uint64_t *ob, uint64_t *oe, uint64_t *first, uint64_t *end) {
+        const int rc = havac_stream_block(blockColumns, tables.prefixSums.back(), k, nsymbols, ob, oe, first, end);
+        if (rc == HAVAC_E_LENGTH)
+            throw std::length_error("the database passes the 2^26 segments of 12288 columns the hit record's segment field can name");
+        if (rc) throw std::logic_error("the search's block planner refused block " + std::to_string(k));
+    };
+
+    if (!boundaryMode_) {
+        // blocks of whole segments; every column is read, scanned and packed once, in file order, and the halo and look-ahead of a
+        // block move device to device from the block before's buffer (havac_dev_stream_submit_text)
+        vector<uint64_t> patchColumns;
+        vector<uint8_t> patchSymbols;
+        uint64_t npad = 0, packedEnd = 0;       // the padded database once its end is read; the columns on the device so far
+        for (uint64_t k = 0; !npad || k * blockColumns < npad; k++) {
+            uint64_t ob, oe, first, end;
+            planned(k, npad, &ob, &oe, &first, &end);
+            patchColumns.clear();
+            patchSymbols.clear();
+            uint64_t got = 0;
+            if (!npad) {
+                const uint64_t want = end - packedEnd;
+                got = reader.readChars(want);
+                if (got < want) {                // the end of the file: padding only there, as in one load
+                    if (reader.columns() == 0) throw std::length_error("the FASTA file holds no sequence");
+                    npad = (reader.columns() + S - 1) / S * S;
+                    planned(k, npad, &ob, &oe, &first, &end);
+                }
+                reader.collectPatches(patchColumns, patchSymbols);
+                noteRecords();
+            }
+            if (inFlight.size() == 2) collect();
+            check(havac_dev_stream_submit_text(dev_, got ? reader.text().data() : nullptr, got, patchColumns.data(), patchSymbols.data(),
+                                               patchColumns.size(), first, end, ob, oe, npad ? npad : end));
+            packedEnd = end;
+            inFlight.push_back(Block{k, ob, oe, 0, RunInputs()});
+            stats.blocks++;
+        }
+    } else {
+        // blocks of whole records, each in the boundary layout of its own (and its second strand); hits resolve against the block's
+        // tables and its first record's index
+        for (uint64_t k = 0;; k++) {
+            const uint64_t got = reader.readRecords(blockColumns);
+            if (got == 0) {
+                if (k == 0) throw std::length_error("the FASTA file holds no sequence");
+                break;
+            }
+            Block b{k, reader.firstColumn(), reader.firstColumn() + got, stats.recordLengths.size(), tables};
+            RunInputs &t = b.boundary;
+            vector<uint64_t> ends;
+            for (const uint64_t e : reader.recordEnds()) ends.push_back(e - reader.firstColumn());
+            t.recordStarts.assign(ends.size(), 0);
+            for (size_t j = 0; j < ends.size(); j++) {
+                const uint64_t len = ends[j] - (j ? ends[j - 1] : 0);
+                t.recordLengths.push_back(len);
+                t.residueCounts.push_back(len - 1);
+                stats.recordLengths.push_back(len - 1);
+            }
+            t.bothStrands = bothStrands_;
+            if (inFlight.size() == 2) collect();
+            check(havac_dev_stream_submit_records(dev_, reader.text().data(), got, ends.data(), (uint32_t)ends.size(), bothStrands_ ? 1 : 0,
+                                                  t.recordStarts.data(), &t.forwardColumns));
+            inFlight.push_back(std::move(b));
+            stats.blocks++;
+        }
+    }
+    while (!inFlight.empty()) collect();
+    stats.columns = reader.columns();
+    stats.records = reader.records();
+    stats.readerPeakBytes = reader.peakTextBytes();
+    return all;
 }
 
 HavacHit::HavacHit(const uint64_t sequencePosition, const uint32_t sequenceIndex, const uint32_t phmmPosition,

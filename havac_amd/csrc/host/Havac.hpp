@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
@@ -63,6 +64,18 @@ struct HavacWindow {
     uint64_t sequenceStart, sequenceEnd;   // inclusive, positions on the record as it stands in the file
     uint32_t phmmFirst, phmmLast;          // lowest / highest model position among the window's hits
     uint32_t hitCount;
+};
+
+// What the last Havac::searchFastaFile read and found (not in the reference).
+struct HavacSearchStats {
+    uint64_t blocks = 0;                   // passes: one per block
+    uint64_t columns = 0;                  // characters of the text (residues and a '\0' per record), padding not counted
+    uint64_t records = 0;
+    uint64_t readerPeakBytes = 0;          // the most text the reader held at once (FastaStream.h)
+    vector<uint64_t> recordLengths;        // residues of every record, as havacMergeHitsToWindows takes them
+    // every block's raw records in block order, when the hits were kept (no onBlock): in the plain mode global columns, the
+    // list one load's run would give; in boundary mode each block's own columns
+    vector<uint64_t> rawHits;
 };
 
 struct havac_dev;   // include/havac_dev.h
@@ -130,6 +143,23 @@ public:
     void setHitCapacity(uint64_t maxHits);                 // the reference's buffer is a fixed 3.5 GiB
     void lastRunMilliseconds(float *ssvKernelMs, float *totalMs);
     const vector<uint64_t> &rawHitsOfLastFetch() const { return rawHits_; }
+    // A streamed search (not in the reference, whose database is loaded whole): the models loaded now against the FASTA file
+    // at `path`, read and scored one block at a time with two passes in flight -- the next block is read, crosses PCIe and is
+    // packed while the pass before runs -- so the database need not fit host or device memory at once.  Plain mode: blocks of
+    // `blockColumns` columns (whole segments); the hits are those of loadSequence + runHardwareClient + getHitsFromFinishedRun on
+    // the same file with the same rand() state, element for element and in the same order.  Boundary mode: blocks of whole
+    // records (at least `blockColumns` characters), one or both strands; the same hits as one load as a multiset.  The plain mode
+    // with both strands is refused (std::logic_error): there one load's reverse half follows the forward half, and a diagonal
+    // runs from the database's last forward columns into its first reverse ones.  0 = kDefaultSearchBlockColumns.  Returns every
+    // hit; with `onBlock` each block's hits are handed over in file order instead and none are kept.  Needs models loaded and no
+    // run in flight (std::logic_error); an empty file is a std::length_error; a block whose hits pass the hit capacity a
+    // std::overflow_error that names the block.  What loadSequence loaded is left as it is.
+    vector<HavacHit> searchFastaFile(const std::string &path, uint64_t blockColumns = 0,
+                                     std::function<void(const vector<HavacHit> &)> onBlock = {});
+    const HavacSearchStats &lastSearchStats() const { return searchStats_; }
+    // 16384 segments (201 M columns, 48 MiB packed): the halo a pass recomputes is under 0.5 % of a block up to models of
+    // 10^6 rows (C3), a pass is long enough to hide the next block's read and upload behind it, and the reader holds 192 MiB
+    static const uint64_t kDefaultSearchBlockColumns = 16384ull * 12288ull;
 
 private:
     void check(int code);                                  // C-ABI code -> the reference's exception types
@@ -170,6 +200,8 @@ private:
     uint32_t pipelineDepth_ = 1;
     vector<HavacHit> fetchHits(RunInputs *inputsOut);
     vector<HavacHit> resolveRun(const RunInputs &run, uint64_t n, RunInputs *inputsOut);
+    static vector<HavacHit> resolveRaw(const vector<uint64_t> &raw, const RunInputs &run, bool boundaryMode);
+    HavacSearchStats searchStats_;
     template <class F>
     auto fetchOldestRun(F &&fetch);
 };

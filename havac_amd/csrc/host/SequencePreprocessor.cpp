@@ -159,18 +159,22 @@ uint64_t nextOther(const unsigned char *chars, uint64_t from, uint64_t count) {
 
 void SequencePreprocessor::collectPatches(const FastaVector *fastaVector, std::vector<uint64_t> &columns,
                                           std::vector<uint8_t> &symbols) {
-    const unsigned char *chars = reinterpret_cast<const unsigned char *>(fastaVector->sequence.charData);
-    const uint64_t count = fastaVector->sequence.count;
     columns.clear();
     symbols.clear();
+    collectPatches(fastaVector->sequence.charData, fastaVector->sequence.count, 0, true, columns, symbols);
+}
+
+void SequencePreprocessor::collectPatches(const char *text, uint64_t count, uint64_t base, bool endsText, std::vector<uint64_t> &columns,
+                                          std::vector<uint8_t> &symbols) {
+    const unsigned char *chars = reinterpret_cast<const unsigned char *>(text);
     for (uint64_t i = nextOther(chars, 0, count); i < count; i = nextOther(chars, i + 1, count)) {
         const uint8_t code = getCompressedSymbol((char)chars[i]);
-        columns.push_back(i);
+        columns.push_back(base + i);
         symbols.push_back((uint8_t)(code & 3u));
         // 'Y' drew 1: the reference ORs 4 << shift into the byte, i.e. sets the low bit of the next symbol of the same
         // byte; every later symbol clears its own field before writing, so the bit survives only behind the last character
-        if (code == 4 && i + 1 == count && (i % 4) != 3) {
-            columns.push_back(i + 1);
+        if (code == 4 && endsText && i + 1 == count && ((base + i) % 4) != 3) {
+            columns.push_back(base + i + 1);
             symbols.push_back(1);
         }
     }

@@ -44,6 +44,10 @@ public:
     // draws 1 sets the low bit of the first padding column).
     static void collectPatches(const struct FastaVector *fastaVector, std::vector<uint64_t> &columns,
                                std::vector<uint8_t> &symbols);
+    // The same rule on a stretch of the text (a streamed search's block, FastaStream.h): `count` characters that start at column
+    // `base` of the whole text, `endsText` when they are its last ones; columns (global) and symbols are APPENDED.
+    static void collectPatches(const char *chars, uint64_t count, uint64_t base, bool endsText, std::vector<uint64_t> &columns,
+                               std::vector<uint8_t> &symbols);
 
 private:
     uint32_t originalLength_ = 0, segments_ = 0, symbols_ = 0, bytes_ = 0;

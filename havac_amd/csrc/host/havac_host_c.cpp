@@ -3,11 +3,13 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <stdexcept>
 #include <string>
 
 #include "../../../include/havac_dev.h"
+#include "FastaStream.h"
 #include "Havac.hpp"
 #include "PhmmPreprocessor.hpp"
 #include "PhmmReprojection.h"
@@ -25,6 +27,7 @@ struct havac_host {
     bool haveDeviceWindows = false;
     uint32_t deviceWindowsFlank = 0;
     uint32_t depth = 1;
+    vector<HavacHit> searchHits;                 // what the last havac_host_search_fasta kept
 };
 
 namespace {
@@ -238,11 +241,94 @@ int havac_host_get_raw_hits(havac_host *h, uint64_t *out, uint32_t cap, uint32_t
     return HAVAC_OK;
 }
 
+int havac_host_search_fasta(havac_host *h, const char *path, uint64_t block_columns, havac_host_block_fn on_block, void *user) {
+    if (!h || !path) return HAVAC_E_ARGUMENT;
+    h->searchHits.clear();
+    return guarded(h, [&] {
+        std::function<void(const vector<HavacHit> &)> each;
+        if (on_block)
+            each = [&](const vector<HavacHit> &hits) {
+                if (hits.size() > 0xffffffffull) throw std::overflow_error("a block's hits do not fit a 32-bit count");
+                const size_t n = hits.size();
+                vector<uint64_t> sp(n);
+                vector<uint32_t> si(n), pp(n), pi(n);
+                vector<uint8_t> rs(n);
+                for (size_t i = 0; i < n; i++) {
+                    sp[i] = hits[i].sequencePosition; si[i] = hits[i].sequenceIndex; pp[i] = hits[i].phmmPosition;
+                    pi[i] = hits[i].phmmIndex; rs[i] = hits[i].reverseStrand ? 1 : 0;
+                }
+                on_block(user, (uint32_t)n, sp.data(), si.data(), pp.data(), pi.data(), rs.data());
+            };
+        h->searchHits = h->obj->searchFastaFile(path, block_columns, each);
+    });
+}
+
+int havac_host_get_search_hits(havac_host *h, uint64_t *sp, uint32_t *si, uint32_t *pp, uint32_t *pi, uint8_t *rs, uint32_t cap,
+                               uint32_t *count) {
+    if (!h) return HAVAC_E_ARGUMENT;
+    const int rc = copyHits(h->searchHits, sp, si, pp, pi, cap, count);
+    if (rc == HAVAC_OK && rs)
+        for (uint32_t i = 0; i < cap && i < h->searchHits.size(); i++) rs[i] = h->searchHits[i].reverseStrand ? 1 : 0;
+    return rc;
+}
+
+int havac_host_search_stats(havac_host *h, uint64_t *blocks, uint64_t *columns, uint64_t *records, uint64_t *peak) {
+    if (!h) return HAVAC_E_ARGUMENT;
+    const HavacSearchStats &s = h->obj->lastSearchStats();
+    if (blocks) *blocks = s.blocks;
+    if (columns) *columns = s.columns;
+    if (records) *records = s.records;
+    if (peak) *peak = s.readerPeakBytes;
+    return HAVAC_OK;
+}
+
+static int copyWords(const vector<uint64_t> &v, uint64_t *out, uint64_t cap, uint64_t *count) {
+    if (count) *count = v.size();
+    for (uint64_t i = 0; i < cap && i < v.size(); i++) out[i] = v[i];
+    return HAVAC_OK;
+}
+int havac_host_get_search_raw_hits(havac_host *h, uint64_t *out, uint64_t cap, uint64_t *count) {
+    return h ? copyWords(h->obj->lastSearchStats().rawHits, out, cap, count) : HAVAC_E_ARGUMENT;
+}
+int havac_host_get_search_record_lengths(havac_host *h, uint64_t *out, uint64_t cap, uint64_t *count) {
+    return h ? copyWords(h->obj->lastSearchStats().recordLengths, out, cap, count) : HAVAC_E_ARGUMENT;
+}
+
 int havac_host_last_run_ms(havac_host *h, float *a, float *b) {
     return guarded(h, [&] { h->obj->lastRunMilliseconds(a, b); });
 }
 
 // ---- host-only stages ------------------------------------------------------
+
+int havac_host_read_fasta_blocks(const char *path, int64_t seed, uint64_t block_chars, int whole_records, char *chars, uint64_t chars_cap,
+                                 uint64_t *nchars, uint64_t *record_ends, uint64_t ends_cap, uint64_t *nrecords, uint64_t *block_ends,
+                                 uint64_t blocks_cap, uint64_t *nblocks, uint64_t *patch_columns, uint8_t *patch_symbols, uint64_t patch_cap,
+                                 uint64_t *npatches, uint64_t *peak) {
+    if (!path || block_chars == 0) return HAVAC_E_ARGUMENT;
+    return guarded(nullptr, [&] {
+        FastaStreamReader reader(path);
+        if (seed >= 0) std::srand((unsigned)seed);
+        uint64_t text = 0, ends = 0, blocks = 0, patches = 0;
+        vector<uint64_t> cols;
+        vector<uint8_t> syms;
+        while (whole_records ? reader.readRecords(block_chars) : reader.readChars(block_chars)) {
+            for (size_t i = 0; i < reader.text().size(); i++, text++)
+                if (text < chars_cap) chars[text] = reader.text()[i];
+            for (const uint64_t e : reader.recordEnds()) { if (ends < ends_cap) record_ends[ends] = e; ends++; }
+            if (blocks < blocks_cap) block_ends[blocks] = text;
+            blocks++;
+            cols.clear(); syms.clear();
+            reader.collectPatches(cols, syms);
+            for (size_t i = 0; i < cols.size(); i++, patches++)
+                if (patches < patch_cap) { patch_columns[patches] = cols[i]; patch_symbols[patches] = syms[i]; }
+        }
+        if (nchars) *nchars = text;
+        if (nrecords) *nrecords = ends;
+        if (nblocks) *nblocks = blocks;
+        if (npatches) *npatches = patches;
+        if (peak) *peak = reader.peakTextBytes();
+    });
+}
 
 int havac_host_pack_fasta(const char *path, int64_t seed, uint8_t *out, uint64_t cap, uint64_t *nbytes,
                           uint64_t *nchars, uint32_t *nrecords) {

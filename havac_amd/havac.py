@@ -45,6 +45,14 @@ HOST_SIGNATURES = {
     "havac_host_get_raw_hits": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     "havac_host_last_run_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "havac_host_last_error": (C.c_char_p, [_vp]),
+    "havac_host_read_fasta_blocks": (C.c_int, [C.c_char_p, C.c_int64, C.c_uint64, C.c_int, _vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                               _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                               _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "havac_host_search_fasta": (C.c_int, [_vp, C.c_char_p, C.c_uint64, _vp, _vp]),
+    "havac_host_get_search_hits": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "havac_host_search_stats": (C.c_int, [_vp] + [C.POINTER(C.c_uint64)] * 4),
+    "havac_host_get_search_raw_hits": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "havac_host_get_search_record_lengths": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "havac_host_pack_fasta": (C.c_int, [C.c_char_p, C.c_int64, _vp, C.c_uint64, C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "havac_host_pack_fasta_layout": (C.c_int, [C.c_char_p, C.c_int64, C.c_int, C.c_int, _vp, C.c_uint64, C.POINTER(C.c_uint64),
@@ -71,6 +79,10 @@ HOST_SIGNATURES = {
 }
 
 _host = None
+
+# havac_host_block_fn (include/havac_host.h)
+_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint8))
 
 
 def load_host() -> C.CDLL:
@@ -222,6 +234,51 @@ class Havac:
         self._check(self._L.havac_host_get_raw_hits(self._h, out.ctypes.data, n.value, C.byref(n)))
         return out
 
+    def searchFastaFile(self, path: str, blockColumns: int = 0, onBlock=None):
+        """Not in the reference: Havac::searchFastaFile -- the loaded models against the FASTA file at `path`, streamed in blocks
+        of `blockColumns` columns (0: the library's default).  Returns every hit; with onBlock(list of HavacHit) each block's hits
+        are handed over in file order instead and an empty list is returned."""
+        trouble = []
+
+        def each(user, n, sp, si, pp, pi, rs):
+            if trouble:
+                return
+            try:
+                onBlock([HavacHit(sp[i], si[i], pp[i], pi[i], bool(rs[i])) for i in range(n)])
+            except BaseException as e:     # (an exception cannot cross the C++ frames: it is raised once the search is over)
+                trouble.append(e)
+
+        callback = _BLOCK_FN(each) if onBlock is not None else None
+        rc = self._L.havac_host_search_fasta(self._h, os.fsencode(path), blockColumns,
+                                             C.cast(callback, C.c_void_p) if callback else None, None)
+        if trouble:
+            raise trouble[0]
+        self._check(rc)
+        if onBlock is not None:
+            return []
+        n = C.c_uint32(0)
+        self._check(self._L.havac_host_get_search_hits(self._h, None, None, None, None, None, 0, C.byref(n)))
+        sp = np.empty(n.value, np.uint64)
+        si, pp, pi = (np.empty(n.value, np.uint32) for _ in range(3))
+        rev = np.zeros(n.value, np.uint8)
+        self._check(self._L.havac_host_get_search_hits(self._h, sp.ctypes.data, si.ctypes.data, pp.ctypes.data, pi.ctypes.data,
+                                                       rev.ctypes.data, n.value, C.byref(n)))
+        return [HavacHit(int(a), int(b), int(c), int(d), bool(e)) for a, b, c, d, e in zip(sp, si, pp, pi, rev)]
+
+    def lastSearchStats(self) -> dict:
+        """Havac::lastSearchStats: blocks, columns, records, readerPeakBytes, and the arrays rawHits (kept when the search had no
+        onBlock) and recordLengths (residues per record, as merge_windows takes them)."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._check(self._L.havac_host_search_stats(self._h, *[C.byref(x) for x in v]))
+        out = dict(zip(("blocks", "columns", "records", "readerPeakBytes"), (x.value for x in v)))
+        for key, fn in (("rawHits", self._L.havac_host_get_search_raw_hits), ("recordLengths", self._L.havac_host_get_search_record_lengths)):
+            n = C.c_uint64(0)
+            self._check(fn(self._h, None, 0, C.byref(n)))
+            arr = np.empty(n.value, np.uint64)
+            self._check(fn(self._h, arr.ctypes.data, n.value, C.byref(n)))
+            out[key] = arr
+        return out
+
     def lastRunMs(self):
         a, b = C.c_float(0), C.c_float(0)
         self._check(self._L.havac_host_last_run_ms(self._h, C.byref(a), C.byref(b)))
@@ -283,6 +340,29 @@ def text_and_patches(path: str, seed: int = -1):
     if rc != 0:
         raise_for(rc, f"could not read {path}")
     return chars, cols, syms
+
+
+def read_fasta_blocks(path: str, block_chars: int, whole_records: bool = False, seed: int = -1) -> dict:
+    """The streamed search's reader alone (havac_host_read_fasta_blocks): the blocks' text, record ends and patches laid end to
+    end, each block's end, and the reader's peak text bytes."""
+    L = load_host()
+    counts = [C.c_uint64(0) for _ in range(5)]
+    nchars, nrecords, nblocks, npatches, peak = counts
+
+    def call(cc, ce, cb, cp, bufs):
+        rc = L.havac_host_read_fasta_blocks(os.fsencode(path), seed, block_chars, int(whole_records), bufs[0], cc, C.byref(nchars),
+                                            bufs[1], ce, C.byref(nrecords), bufs[2], cb, C.byref(nblocks), bufs[3], bufs[4], cp,
+                                            C.byref(npatches), C.byref(peak))
+        if rc != 0:
+            raise_for(rc, f"reading {path} in blocks")
+
+    call(0, 0, 0, 0, [None] * 5)
+    chars = np.empty(nchars.value, np.uint8)
+    ends, blocks, cols = (np.empty(n, np.uint64) for n in (nrecords.value, nblocks.value, npatches.value))
+    syms = np.empty(npatches.value, np.uint8)
+    call(chars.size, ends.size, blocks.size, cols.size, [a.ctypes.data for a in (chars, ends, blocks, cols, syms)])
+    return {"chars": chars.tobytes(), "record_ends": ends, "block_ends": blocks, "patch_columns": cols, "patch_symbols": syms,
+            "peak": peak.value}
 
 
 def pack_fasta_layout(path: str, boundary_mode: bool, both_strands: bool, seed: int = -1):

@@ -243,6 +243,45 @@ int havac_windows_join(uint64_t nwindows, const uint64_t *list_ends, uint32_t nl
                        uint8_t *reverse_strand, uint64_t *sequence_start, uint64_t *sequence_end, uint32_t *phmm_first,
                        uint32_t *phmm_last, uint32_t *hit_count, uint64_t *count);
 
+/* ------------------------------------------------------------------------
+ * Level 1b: a streamed search (Havac::searchFastaFile; no counterpart in the reference, whose database is loaded whole)
+ * ---------------------------------------------------------------------- */
+/* The block planner (host arithmetic, no device).  Plain mode: block k of a stream cut into blocks of block_columns columns (a
+ * positive multiple of 12288) owns [own_begin, own_end) = [k B, min((k+1) B, nsymbols)), and its pass reads the columns
+ * [first_column, end_column) that havac_ssv_shard_window would name for that range -- the left halo of nrows - 1 columns plus the
+ * tiling's reach, and the look-ahead on the right.  nsymbols: the database's padded column count, or 0 while it is not known (the
+ * database then goes on past the look-ahead).  HAVAC_E_ARGUMENT for a block at or past nsymbols, HAVAC_E_LENGTH past the 2^26
+ * segments the hit record's segment field holds. */
+int havac_stream_block(uint64_t block_columns, uint32_t nrows, uint64_t block_index, uint64_t nsymbols, uint64_t *own_begin,
+                       uint64_t *own_end, uint64_t *first_column, uint64_t *end_column);
+/* A streamed search on the handle's first GPU, against the model written last: a pipe of its own with two passes in flight and two
+ * block buffers that alternate, so that block k + 1 crosses PCIe and is packed while the pass of block k runs.  What the handle's
+ * other entry points loaded -- its sequence, separator bitmap, runs -- is left as it is.  _open: HAVAC_E_LOGIC while a run of the
+ * handle is in flight or no model is written; it closes a search left open.  _close waits for what is in flight and frees it all. */
+int havac_dev_stream_open(havac_dev *dev);
+int havac_dev_stream_close(havac_dev *dev);
+/* Plain mode (the reference's layout): the next block's pass over an owned range (havac_stream_block's four columns) with
+ * `nsymbols` columns known so far (>= end_column; the database's padded count once its end is read).  The buffer's columns
+ * [first_column, from) -- `from` being where the block before's buffer ended, 0 for the first block -- are carried device to device
+ * from the block before's buffer (first_column may not lie before that buffer's first column); `chars` (nchars <= end_column -
+ * from) is the text of the columns from `from` on, packed as havac_dev_write_sequence_chars packs, with its patches (global
+ * columns, ascending, in [from, end_column)); columns behind the text are symbol 0.  HAVAC_E_LOGIC when both passes are in flight. */
+int havac_dev_stream_submit_text(havac_dev *dev, const char *chars, uint64_t nchars, const uint64_t *patch_columns,
+                                 const uint8_t *patch_symbols, uint64_t npatches, uint64_t first_column, uint64_t end_column,
+                                 uint64_t own_begin, uint64_t own_end, uint64_t nsymbols);
+/* Boundary mode: the next block is a group of whole records laid out as havac_dev_write_sequence_records lays them out (record_ends
+ * relative to `chars`), followed, with both_strands != 0, by its second strand (havac_dev_append_reverse_strand); one pass over all
+ * of it.  record_starts_out (nrecords entries, may be NULL): each record's first column in the block; *forward_columns_out: the
+ * forward half's columns with both strands, else 0. */
+int havac_dev_stream_submit_records(havac_dev *dev, const char *chars, uint64_t nchars, const uint64_t *record_ends, uint32_t nrecords,
+                                    int both_strands, uint64_t *record_starts_out, uint64_t *forward_columns_out);
+/* Completes the oldest pass in flight: *count = the hits it found (HAVAC_E_HIT_OVERFLOW when they passed the handle's hit capacity).
+ * Its records, in device order and in global columns (boundary mode: the block's columns), are read with _read_hits until the
+ * next submit. */
+int havac_dev_stream_collect(havac_dev *dev, uint64_t *count);
+int havac_dev_stream_read_hits(havac_dev *dev, uint64_t *out, uint64_t n);
+uint32_t havac_dev_stream_in_flight(havac_dev *dev);
+
 /* Device time of the last completed run in milliseconds (HIP events on the
  * handle's stream): the SSV kernel alone, and the whole enqueue (model
  * padding copy + SSV + hit ordering). */
@@ -295,6 +334,12 @@ int havac_ssv_enqueue(havac_ssv_ctx *ctx, const uint8_t *d_sequence, uint64_t ns
 int havac_ssv_shard_window(uint64_t nsymbols, uint32_t nrows, uint32_t shard_index, uint32_t shard_count,
                            uint64_t *first_column, uint64_t *end_column);
 int havac_ssv_set_sequence_window(havac_ssv_ctx *ctx, uint64_t first_column, uint64_t ncolumns);
+/* Optional: the next passes own the explicit column range [col_begin, col_end) (whole segments) instead of shard shard_index of
+ * shard_count, which must then be 0 of 1; nsymbols is the number of columns known so far -- at least col_end, the database's total
+ * once known -- and may pass the 4 GiB of one buffer (the sequence window may not) up to the 2^26 segments of the hit record.  Hits
+ * are reported for the range only, in global columns; columns at and past nsymbols read as outside the database.  (0, 0) = the
+ * shard's columns again (the default).  A streamed search runs its blocks this way (havac_stream_block). */
+int havac_ssv_set_owned_columns(havac_ssv_ctx *ctx, uint64_t col_begin, uint64_t col_end);
 
 /* Separator bitmap for the next passes (see havac_dev_write_separator_mask); a DEVICE pointer the caller keeps
  * alive, 2-byte aligned, nsymbols/16 bytes; NULL (the default) = none. */

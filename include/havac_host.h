@@ -56,6 +56,22 @@ int havac_host_get_raw_hits(havac_host *h, uint64_t *out, uint32_t cap, uint32_t
 int havac_host_last_run_ms(havac_host *h, float *ssv_kernel_ms, float *total_ms);
 const char *havac_host_last_error(havac_host *h);
 
+/* Havac::searchFastaFile (not in the reference): the loaded models against the FASTA file at fasta_path, streamed in blocks of
+ * block_columns columns (0: the library's default).  With on_block, every block's hits are handed to it in file order (the arrays
+ * are valid during the call; reverse_strand one byte per hit) and none are kept; without, they are kept on the handle for
+ * havac_host_get_search_hits.  Exceptions as the C++ method throws them, as HAVAC_E_* codes. */
+typedef void (*havac_host_block_fn)(void *user, uint32_t nhits, const uint64_t *sequence_position, const uint32_t *sequence_index,
+                                    const uint32_t *phmm_position, const uint32_t *phmm_index, const uint8_t *reverse_strand);
+int havac_host_search_fasta(havac_host *h, const char *fasta_path, uint64_t block_columns, havac_host_block_fn on_block, void *user);
+/* the hits the last search kept: first call with cap = 0 to learn the count (reverse_strand may be NULL) */
+int havac_host_get_search_hits(havac_host *h, uint64_t *sequence_position, uint32_t *sequence_index, uint32_t *phmm_position,
+                               uint32_t *phmm_index, uint8_t *reverse_strand, uint32_t cap, uint32_t *count);
+/* Havac::lastSearchStats: blocks, text columns, records, the reader's peak text bytes (any pointer may be NULL); the raw records
+ * the last search kept and every record's residue count, count-then-arrays */
+int havac_host_search_stats(havac_host *h, uint64_t *blocks, uint64_t *columns, uint64_t *records, uint64_t *reader_peak_bytes);
+int havac_host_get_search_raw_hits(havac_host *h, uint64_t *out, uint64_t cap, uint64_t *count);
+int havac_host_get_search_record_lengths(havac_host *h, uint64_t *out, uint64_t cap, uint64_t *count);
+
 /* ---- host-only stages, no device needed -------------------------------- */
 
 /* FastaVector + SequencePreprocessor: file -> 2-bit packed, segment-padded bytes.
@@ -101,6 +117,15 @@ int havac_host_pack_fasta_layout(const char *fasta_path, int64_t seed, int bound
  * in havac_host_pack_fasta.  Writes at most `cap` characters / patches; *nchars, *npatches = the full counts. */
 int havac_host_text_and_patches(const char *fasta_path, int64_t seed, char *chars, uint64_t chars_cap, uint64_t *nchars,
                                 uint64_t *patch_columns, uint8_t *patch_symbols, uint64_t patch_cap, uint64_t *npatches);
+
+/* The streamed search's reader alone (FastaStream.h): the file read in blocks of `block_chars` characters (whole_records != 0:
+ * blocks of whole records of at least that many), seed as in havac_host_pack_fasta; the blocks' characters, record ends (global)
+ * and patches (FastaStreamReader::collectPatches, block by block) laid end to end, each block's end, and the most text one block
+ * held.  Writes at most the given capacities; the counts are the full ones. */
+int havac_host_read_fasta_blocks(const char *fasta_path, int64_t seed, uint64_t block_chars, int whole_records, char *chars,
+                                 uint64_t chars_cap, uint64_t *nchars, uint64_t *record_ends, uint64_t ends_cap, uint64_t *nrecords,
+                                 uint64_t *block_ends, uint64_t blocks_cap, uint64_t *nblocks, uint64_t *patch_columns,
+                                 uint8_t *patch_symbols, uint64_t patch_cap, uint64_t *npatches, uint64_t *peak_text_bytes);
 
 /* Hits -> merged windows (Havac.hpp: havacMergeHitsToWindows).  `reverse_strand` may
  * be NULL (all forward).  Writes at most `cap` windows into the seven output arrays, *count = windows found. */
